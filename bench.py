@@ -156,9 +156,11 @@ def np_asarray_u32(x):
     return np.ascontiguousarray(x, dtype=np.uint32)
 
 
-def get_compiled(name: str, batch: int, cache_root: str, rank: int, dist):
+def get_compiled(name: str, batch: int, cache_root: str, rank: int, dist, flat: bool = True):
     """Rank 0 traces + lowers the circuit once (or finds the artefacts of this exact source in the cache); the other
-    ranks wait and load the files.  Every rank traces + flattens (seconds) to have the flat code for the oracle."""
+    ranks wait and load the files.  Every rank traces + flattens (seconds) to have the flat code for the oracle;
+    `flat=False` (a plain bench run, which never asks the oracle) leaves that out where the artefacts are cached:
+    `Compiled.flat` is then None."""
     from circom_amd import compiler
     from circom_amd.frontend.flatten import flatten
     from circom_amd.hip_elements import writers
@@ -171,35 +173,55 @@ def get_compiled(name: str, batch: int, cache_root: str, rank: int, dist):
         strands = (1,) + tuple(strands)
     if os.environ.get("CW_BENCH_STRANDS"):          # experiments: lower (only) this strand count
         strands = (int(os.environ["CW_BENCH_STRANDS"]),)
-    d = os.path.join(cache_root, "%s_s%s_b%s_m%s_%s" % (name, "-".join(map(str, strands)), os.environ.get("CW_BITS", "1"),
-                                                       os.environ.get("CW_MONT", "a"), fp))
+    key = "%s_s%s_b%s_m%s_%s" % (name, "-".join(map(str, strands)), os.environ.get("CW_BITS", "1"), os.environ.get("CW_MONT", "a"), fp)
+    # The cache may be read-only for this user.  Then an entry that is there is used where it lies, and what has to be
+    # written goes to `w`, this user's own entry of the same key under the temporary directory: the lock, files unpacked
+    # from their compressed form, and the whole lowering when the cache has no entry.  Every rank decides alike.
+    try:
+        os.makedirs(cache_root, exist_ok=True)
+    except OSError:
+        pass
+    d = w = os.path.join(cache_root, key)
+    if not os.access(cache_root, os.W_OK | os.X_OK):
+        w = os.path.join(tempfile.gettempdir(), "cw_bench_cache_%d" % os.getuid(), key)
+        if not os.path.exists(os.path.join(d, "done")):
+            d = w
     p = lambda ext: os.path.join(d, name + ext)
+    # (a large artefact that lies compressed in a read-only entry is unpacked into `w`)
+    at = lambda ext: p(ext) if d == w or os.path.exists(p(ext)) else os.path.join(w, name + ext)
     t0 = time.perf_counter()
-    fc = flatten(make_program(name))
     done = os.path.join(d, "done")
+    fc = flatten(make_program(name)) if flat or not os.path.exists(done) else None
     lock = None
     if rank == 0:
         # several processes of one box may want the same artefacts (pytest-xdist workers): one lowers, the others wait and load
         import fcntl
-        os.makedirs(cache_root, exist_ok=True)
-        lock = open(d + ".lock", "w")
+        os.makedirs(os.path.dirname(w), exist_ok=True)
+        lock = open(w + ".lock", "w")
         fcntl.flock(lock, fcntl.LOCK_EX)
     cached = os.path.exists(done)
     if cached and rank == 0:
-        # large artefacts travel compressed (tools/prebuild_cache.py: the .r1cs of the ECDSA verifier is 407 MB, 34 MB gzipped)
-        # (.xz for the 53-block SHA-256, tools/r06_prebuild_27008.sh: 1.7 GB of tables in 93 MB - gzip leaves 254 MB, and the gpurun
-        # snapshot has a size limit)
+        # large artefacts travel compressed (tools/prebuild_cache.py: the .r1cs of the ECDSA verifier is 407 MB, 34 MB gzipped;
+        # .xz for the 53-block SHA-256, tools/r06_prebuild_27008.sh: 1.7 GB of tables in 93 MB - gzip leaves 254 MB)
         import gzip
         import lzma
         import shutil
         for ext in (".cwt", ".dat", ".r1cs"):
             for suffix, opener in ((".gz", gzip.open), (".xz", lzma.open)):
-                if not os.path.exists(p(ext)) and os.path.exists(p(ext) + suffix):
-                    with opener(p(ext) + suffix, "rb") as fi, open(p(ext) + ".tmp", "wb") as fo:
-                        shutil.copyfileobj(fi, fo, 1 << 24)
-                    os.replace(p(ext) + ".tmp", p(ext))
+                if not os.path.exists(at(ext)) and os.path.exists(p(ext) + suffix):
+                    tmp = at(ext) + ".tmp%d" % os.getpid()
+                    try:
+                        os.makedirs(w, exist_ok=True)
+                        with opener(p(ext) + suffix, "rb") as fi, open(tmp, "wb") as fo:
+                            shutil.copyfileobj(fi, fo, 1 << 24)
+                        os.replace(tmp, at(ext))
+                    except OSError as ex:
+                        raise RuntimeError("bench: cannot unpack %s to %s (%s): neither the cache nor the temporary directory "
+                                           "can be written" % (p(ext) + suffix, at(ext), ex)) from ex
     if rank == 0 and not cached:
         os.makedirs(d, exist_ok=True)
+        if fc is None:                  # (the cache entry went away between the look above and the lock)
+            fc = flatten(make_program(name))
         bittape, bitnet = (None, None) if os.environ.get("CW_BITS", "1") == "0" else compiler.lower_bitplane_net(fc)
         mont = compiler.choose_mont(fc)     # arithmetic circuits keep their signals in Montgomery form on the device
         if os.environ.get("CW_MONT"):
@@ -227,7 +249,7 @@ def get_compiled(name: str, batch: int, cache_root: str, rank: int, dist):
         lock.close()                    # (releases the flock)
     if dist:
         dist.barrier()
-    cp = compiler.Compiled(name, d, p(".cwt"), p(".dat"), p(".r1cs"), p(".sym"), fc, None)
+    cp = compiler.Compiled(name, d, at(".cwt"), at(".dat"), at(".r1cs"), p(".sym"), fc, None)
     try:
         cp.jit_stats = json.load(open(p(".jit.json")))
     except Exception:
@@ -406,6 +428,44 @@ def golden_messages(workload: str):
         return []
     g = json.load(open(f))
     return [(bytes.fromhex(v["message_hex"]), v["wtns_sha256"], int(v["wtns_len"])) for v in g.get("vectors", ()) if "message_hex" in v]
+
+
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, batch, circ, d_pub=None):
+    """`--dump-outputs DIR`: what a caller of the timed path holds after its last step, as DIR/<name>.npy in float64, at most
+    40 MiB in all.  Field elements are written as their eight little-endian 32-bit limbs (exact in float64).
+      status.npy                     [S]         the per-instance status words (every instance up to 2^20, else a seeded sample)
+      status_instances.npy           [S]         the instances they belong to
+      public_signals.npy             [P][n_public][8]   public signals of a seeded sample of instances (d_pub: the device image
+      public_signals_instances.npy   [P]                [B][n_public][32] that cw_public_signals_device wrote)
+      witness_sample.npy             [2][W][8]   seeded wires of the first and the last instance's witness (cw_get_witness)
+      witness_sample_wires.npy       [W]
+    The samples depend on the shapes and DUMP_SEED only, so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    B = batch.n
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = lambda n, k: np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+    limbs = lambda a: np.ascontiguousarray(a).view("<u4").astype(np.float64)
+    out = {}
+    si = pick(B, 1 << 20)
+    out["status"] = batch.status()[si].astype(np.float64)
+    out["status_instances"] = si.astype(np.float64)
+    if d_pub is not None and circ.n_public:
+        import torch
+        pi = pick(B, max(1, (16 << 20) // (64 * circ.n_public)))
+        rows = d_pub[torch.from_numpy(pi).to(d_pub.device)].cpu().numpy()          # [P][n_public][32]
+        out["public_signals"] = limbs(rows).reshape(len(pi), circ.n_public, 8)
+        out["public_signals_instances"] = pi.astype(np.float64)
+    wi = pick(circ.n_witness, 32768)
+    wit = [np.frombuffer(batch.witness_bytes(i), dtype=np.uint8).reshape(circ.n_witness, -1)[wi] for i in sorted({0, B - 1})]
+    out["witness_sample"] = limbs(np.stack(wit)).reshape(len(wit), len(wi), -1)
+    out["witness_sample_wires"] = wi.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return {"dir": dirname, "files": sorted(out), "bytes": int(sum(v.nbytes for v in out.values()))}
 
 
 def parity_check(cp, circ, batch, h_in, workload: str, n_sample: int = 4, digest_bits=None, golden_at=None):
@@ -604,8 +664,9 @@ def goldilocks_bench(args):
     elapsed = time.perf_counter() - t0
     st = batches[0].status()
     assert (st == 0).all(), "failed instances on the goldilocks workload"
-    # parity: full .wtns bytes of a few instances
-    picks = sorted({0, 1, B // 2, B - 1})
+    dumped = dump_outputs(args.dump_outputs, batches[(args.steps - 1) % n_fl], circ) if args.dump_outputs else None
+    # parity: full .wtns bytes of a few instances (--full)
+    picks = sorted({0, 1, B // 2, B - 1}) if args.full else []
     cli = ROOT / "oracle" / "_ref" / "goldilocks" / name
     par = {"instances": picks}
     for i in picks:
@@ -639,7 +700,7 @@ def goldilocks_bench(args):
     roof_chk = {"bound": "hbm", "kernel": "cw64_r1cs_kernel", "unit": "GB/s", "achieved": alg_chk / (iso["check"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                 "frac": alg_chk / (iso["check"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel_ms": iso["check"], "algorithmic_bytes_per_launch": alg_chk}
     cpu = None
-    if not args.no_cpu_baseline and cli.exists():
+    if args.full and not args.no_cpu_baseline and cli.exists():
         from oracle import ref_build
         import concurrent.futures as cf
         cores = ref_build.host_cores()[0]
@@ -663,7 +724,7 @@ def goldilocks_bench(args):
         "config": {"workload": "poseidon2 goldilocks --O0 (%d constraints), batch=%d" % (circ.n_constraints, B), "n_signals": circ.n_signals,
                    "n_witness": n_wit, "engine": "64-bit runtime on the device (csrc/cw64.hip)", "in_flight": n_fl, "compile_s": compile_s},
         "roofline": roof, "roofline_r1cs": roof_chk, "isolated": {"kernels_ms": iso}, "parity": par, "parity_checked": par["parity_checked"],
-        "failed_instances": 0, "cpu_baseline": cpu}))
+        "failed_instances": 0, "cpu_baseline": cpu, "full": bool(args.full), "outputs_dumped": dumped}))
     for b_ in batches:
         b_.close()
     circ.close()
@@ -687,6 +748,14 @@ def main():
     ap.add_argument("--packed-inputs", action="store_true",
                     help="boolean circuits: the batch's inputs enter as packed masks (cw_set_inputs_bits_device, one bit per "
                          "input and instance) in the timed steps too; the canonical 32-byte image is never materialised")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this benchmark measures and checks: parity with the oracle, "
+                         "canonical egress, packed inputs, the stand-alone audit, Fp-mul/s, the batch-4096 side measurement, per-kernel "
+                         "rooflines and the CPU baseline (minutes).  Without it the run sets up, warms up, times the steps and prints "
+                         "the headline fields of the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step (status words, public signals, sampled witness "
+                         "wires) as DIR/<name>.npy: see dump_outputs.  With --gpus N it is rank 0's shard")
     ap.add_argument("--parity-instances", type=int, default=4)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -760,7 +829,7 @@ def main():
         B = hi - lo
     cache_root = args.cache_dir or (str(ROOT / "gpurun_in" / "cache") if (ROOT / "gpurun_in" / "cache").is_dir()
                                     else os.path.join(tempfile.gettempdir(), "cw_bench_cache_%d" % os.getuid()))
-    cp, compile_s, compile_cached = get_compiled(args.workload, B, cache_root, rank, dist)
+    cp, compile_s, compile_cached = get_compiled(args.workload, B, cache_root, rank, dist, flat=args.full)
     circ = rt.Circuit(cp.tape_path, cp.dat_path, cp.r1cs_path)
     if args.workload == "sha256_2048":
         assert circ.n_constraints >= 1_000_000, "the metric's workload must have >= 1M constraints"
@@ -805,7 +874,7 @@ def main():
             pos_ = 0 if k_ == 0 else B - k_                 # the first golden at instance 0, the others at the end of the batch
             d_bits[pos_] = torch.from_numpy(np.unpackbits(np.frombuffer(msg_, dtype=np.uint8))).to(dev)
             golden_at[pos_] = (msg_, sha_, len_)
-        h_in = BoolInputs(d_bits.cpu().numpy())
+        h_in = BoolInputs(d_bits.cpu().numpy()) if args.full or args.packed_inputs else None     # (4 GB to the host: oracle / packed masks only)
         if args.packed_inputs:
             main_masks = h_in.masks()
             d_in = torch.from_numpy(main_masks.view(np.int64)).to(dev)
@@ -928,12 +997,13 @@ def main():
         if dist:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        n_plain = min(args.steps, 64 * n_fl) if args.full else 0     # (steps of its own for per-kernel figures: --full)
         for b_ in batches:
             b_.set_timing("history")
-        for s in range(min(args.steps, 64 * n_fl)):           # the plain pass: in-step kernel durations, generation / check split
+        for s in range(n_plain):                              # the plain pass: in-step kernel durations, generation / check split
             step(s, evs[s])
         torch.cuda.synchronize()
-        evs = evs[:min(args.steps, 64 * n_fl)]
+        evs = evs[:n_plain]
     else:
         # from here on every run of every batch keeps its own marks (cw_batch_set_timing(b, 2), a ring of 64): the kernels' durations
         # INSIDE the timed region are averages over all its steps - what a rocprofv3 kernel trace of the region averages to
@@ -973,21 +1043,30 @@ def main():
     status = gather_status(torch.from_numpy(batch.status().astype(np.int32)).to(dev), dist, rank, world)
     n_bad = int((status != 0).sum().item()) if rank == 0 else 0
     n_total = int(status.numel()) if rank == 0 else 0
-    pub = torch.empty((B, circ.n_public, 32), dtype=torch.uint8, device=dev)
-    if circ.n_public:
+    # (a plain run without --dump-outputs has no use for the public signals: their image is 17 GB for the default batch)
+    want_pub = bool(args.full or args.dump_outputs or dist)
+    pub = torch.empty((B if want_pub else 0, circ.n_public, 32), dtype=torch.uint8, device=dev)
+    if circ.n_public and want_pub:
         batch.public_signals_device(pub.data_ptr())
         torch.cuda.synchronize()
     pub_local = pub
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = batches[(args.steps - 1) % n_fl]             # the batch the last timed step ran on
+        if last is not batch and circ.n_public:
+            last.public_signals_device(pub.data_ptr())        # (every batch in flight computed the same instances: checked above)
+            torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, last, circ, pub if circ.n_public else None)
     # (bit-level circuits send one bit per public signal: 2^21 SHA-256 digests are 64 MB per rank, not 17 GB)
-    pub, pub_form = gather_public(pub, dist, rank, world)
+    pub, pub_form = gather_public(pub, dist, rank, world) if want_pub else (pub, None)
     n_pub_gathered = int(pub.shape[0]) if rank == 0 else 0
     pub_bytes_per_instance = (int(pub.shape[1]) if pub_form == "bits" else 32 * circ.n_public) if rank == 0 else 0
 
-    gen_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / len(evs)
-    chk_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / len(evs)
+    gen_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / len(evs) if evs else None
+    chk_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / len(evs) if evs else None
 
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         dg_bits = None
         if args.workload.startswith("sha256_") and circ.n_public >= 256:
             assert not bool(pub_local[:, :256, 1:].any().item()), "digest signals are not bits"
@@ -1000,7 +1079,7 @@ def main():
     # Timed on a slice of the batch (the image of a 1M-signal circuit is 32 MB per instance: 2.1 TB for 65 536) alone,
     # and while the OTHER batch in flight keeps evaluating + checking on its own stream (the overlapped pipeline)
     egress = None
-    if rank == 0:
+    if args.full and rank == 0:
         row_bytes = circ.n_witness * 32
         chunk = max(1, min(B, (1 << 30) // row_bytes))
         n_e = min(B, chunk * 8)
@@ -1072,7 +1151,7 @@ def main():
 
     # packed boolean inputs (cw_set_inputs_bits_device): one bit per input and instance instead of 32 bytes
     packed = None
-    if rank == 0 and batch.bitmode and args.workload.startswith("sha256_") and not args.packed_inputs:
+    if args.full and rank == 0 and batch.bitmode and args.workload.startswith("sha256_") and not args.packed_inputs:
         masks = (h_in if isinstance(h_in, BoolInputs) else BoolInputs(np.ascontiguousarray(h_in[:, :, 0]))).masks()
         d_masks = torch.from_numpy(masks.view(np.int64)).to(dev)
         for b_ in batches:
@@ -1106,7 +1185,7 @@ def main():
     # the stand-alone audit of an emitted-code batch (what a sceptical caller runs: CW_R1CS_AUDIT=1 re-checks every constraint
     # from the table instead of trusting the fused check): the emitted audit program, and the general kernels for comparison
     audit = None
-    if rank == 0 and batch.bitmode and batch.jit and not args.no_small:
+    if args.full and rank == 0 and batch.bitmode and batch.jit and not args.no_small:
         audit = {}
         for key_, envs in (("emitted_audit_ms", {"CW_R1CS_AUDIT": "1"}), ("general_kernels_ms", {"CW_R1CS_AUDIT": "1", "CW_R1CS_AUDIT_GENERAL": "1"})):
             os.environ.update(envs)
@@ -1121,7 +1200,7 @@ def main():
 
     # Fp mul/s half of the metric: 2^24 lanes x 1024 dependent Montgomery products, bn128 and bls12381
     fp_mul = {}
-    if rank == 0:
+    if args.full and rank == 0:
         from circom_amd.field import PRIMES
         rng = np.random.default_rng(5)
         n = args.fp_bench_lanes
@@ -1136,7 +1215,7 @@ def main():
 
     # the batch BASELINE.json's configs use for SHA-256 (4096), measured next to the throughput batch
     small = None
-    if rank == 0 and world == 1 and args.workload == "sha256_2048" and B > 4096 and not args.batch and not args.no_small:
+    if args.full and rank == 0 and world == 1 and args.workload == "sha256_2048" and B > 4096 and not args.batch and not args.no_small:
         b2 = circ.batch(4096, device=local_rank, stream=stream.cuda_stream)
         set_in(b2)
         ev2 = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(4)]
@@ -1150,7 +1229,35 @@ def main():
                  "lanes_per_wave": b2.lanes}
         b2.close()
 
+    dtype = (("bit-plane boolean gates (v_bitop3_b32 on u32 lanes of 32 instances, emitted per circuit; u256 Montgomery fallback for "
+              "non-boolean instances)") if batch.bitmode and batch.jit else
+             "bit-plane boolean gates on u64 instance masks (u256 Montgomery fallback for non-boolean instances)" if batch.bitmode
+             else "u256 (9x29-bit limbs, Montgomery multiply)")
     if rank == 0:
+        # the headline fields and what the timed region itself measured: the plain run's line; --full adds to it below
+        from circom_amd.field import PRIMES
+        prime = next((k_ for k_, v_ in PRIMES.items() if v_ == circ.q), "?")
+        head = {
+            "metric": "witnesses/sec (batched inputs)", "value": n_total * args.steps / elapsed, "unit": "witnesses/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": dtype, "data": "synthetic", "full": bool(args.full),
+            "config": {"workload": "%s %s --O0 (%d constraints), batch=%d per GPU" % (args.workload, prime, circ.n_constraints, B),
+                       "n_signals": circ.n_signals, "n_witness": circ.n_witness, "n_constraints": circ.n_constraints,
+                       "in_flight": n_fl, "step_launch": "one HIP graph per step (cw_run_check)" if use_graph else "plain launches (cw_run + cw_check_r1cs)",
+                       "lanes_per_wave": batch.lanes, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
+                       "compile_s": compile_s, "compile_cached": compile_cached, "shard_of": args.shard_of or None,
+                       "total_batch": args.total_batch or None},
+            # eval_ms / r1cs_check_ms: HIP-event intervals inside the timed region (with in_flight > 1 the regions of
+            # consecutive steps overlap on the GPU, so each is stretched by the other batch's kernels and they add up to
+            # more than ms_per_step); `isolated`: one step running alone; roofline*.kernel_ms: the kernel's own duration
+            # (in_step_kernels_ms: ingest / eval / check, event pairs on each batch's stream, inside the timed region)
+            "eval_ms": gen_ms, "r1cs_check_ms": chk_ms, "isolated": isolated, "in_step_kernels_ms": in_step,
+            "failed_instances": n_bad, "parity_checked": 0, "outputs_dumped": dumped,
+            "gathered": {"status_words": n_total, "public_signal_rows": n_pub_gathered,
+                         "public_signals_per_instance": circ.n_public, "public_signals_sent_as": pub_form,
+                         "bytes_per_instance": 4 + pub_bytes_per_instance}}
+        line = json.dumps(head)
+    if rank == 0 and args.full:
         total_witnesses = n_total * args.steps
         value = total_witnesses / elapsed
         n_in, n_wit = circ.n_inputs, circ.n_witness
@@ -1389,23 +1496,9 @@ def main():
         # egress of the whole batch, sequentially; with the egress overlapped (another batch evaluating meanwhile) the step
         # hides behind it
         value_canonical = egress["witnesses_per_s_with_egress"] if egress else None
-        out = {
-            "metric": "witnesses/sec (batched inputs)",
-            "value": value,
-            "unit": "witnesses/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": ("bit-plane boolean gates (v_bitop3_b32 on u32 lanes of 32 instances, emitted per circuit; u256 Montgomery fallback for "
-                      "non-boolean instances)") if batch.bitmode and batch.jit else
-            "bit-plane boolean gates on u64 instance masks (u256 Montgomery fallback for non-boolean instances)" if batch.bitmode
-            else "u256 (9x29-bit limbs, Montgomery multiply)",
-            "data": "synthetic",
-            "config": {"workload": "%s %s --O0 (%d constraints), batch=%d per GPU" % (args.workload, cp.flat.prime, circ.n_constraints, B),
+        out = dict(head)
+        out.update({
+            "config": dict(head["config"], **{
                        "value_is": ("witness generated + R1CS-verified per second, resident as bit planes (1 bit per signal value and "
                                     "instance); value_canonical includes writing the 32-byte-per-element image") if batch.bitmode else
                        ("witness generated + R1CS-verified per second, resident as 32-byte field elements in the value table "
@@ -1426,7 +1519,7 @@ def main():
                                                           if use_graph else "plain launches (cw_run + cw_check_r1cs)"),
                        "cu_partitions": args.cu_partitions or None, "lanes_per_wave": batch.lanes, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
                        "compile_s": compile_s, "compile_cached": compile_cached, "compile_s_cold": getattr(cp, "compile_s_cold", None),
-                       "shard_of": args.shard_of or None, "total_batch": args.total_batch or None},
+                       "shard_of": args.shard_of or None, "total_batch": args.total_batch or None}),
             "value_canonical": value_canonical,
             "value_canonical_hbm_frac": (egress["frac_of_hbm_peak"] if egress else None),
             # the dominant kernel of THIS run (longest measured duration)
@@ -1447,21 +1540,10 @@ def main():
             "batch_4096": small,
             "fp_mul_per_s": fp_mul_per_s,
             "fp_mul_per_s_by_prime": fp_mul,
-            # eval_ms / r1cs_check_ms: HIP-event intervals inside the timed region (with in_flight > 1 the regions of
-            # consecutive steps overlap on the GPU, so each is stretched by the other batch's kernels and they add up to
-            # more than ms_per_step); `isolated`: one step running alone; roofline*.kernel_ms: the kernel's own duration
-            "eval_ms": gen_ms,
-            "r1cs_check_ms": chk_ms,
-            "isolated": isolated,
-            "in_step_kernels_ms": in_step,             # ingest / eval / check: event pairs on each batch's stream, inside the timed region
-            "failed_instances": n_bad,
             "parity": parity,
             "parity_checked": parity["parity_checked"] if parity else 0,
-            "gathered": {"status_words": n_total, "public_signal_rows": n_pub_gathered,
-                         "public_signals_per_instance": circ.n_public, "public_signals_sent_as": pub_form,
-                         "bytes_per_instance": 4 + pub_bytes_per_instance},
             "cpu_baseline": None,
-        }
+        })
         if args.shard_of:
             # BASELINE config 4 is ONE job of `total_batch` instances over `shard_of` GPUs: every GPU runs its shard once.  The
             # steady-state `value` above keeps several shards in flight on this GPU; the job itself costs one shard's latency

@@ -30,8 +30,10 @@ def binaries(prime: str, name: str):
     return d / name, d / (name + "_loop")
 
 
-def build_circuit(cp, force=False):
-    """cp: Compiled.  Returns (cli_binary, loop_binary) or raises if it cannot be built."""
+def build_circuit(cp, force=False, later=None):
+    """cp: Compiled.  Returns (cli_binary, loop_binary) or raises if it cannot be built.
+    later: a list - the compilation is not run here but appended to it as a callable (build_default_circuits runs those of
+    all its circuits side by side: each is minutes of ONE g++ process)."""
     from . import emit_ref_cpp
     from circom_amd.hip_elements.writers import hashmap_size
     prime = cp.flat.prime
@@ -63,10 +65,17 @@ def build_circuit(cp, force=False):
     shutil.copyfile(cp.dat_path, d / (cp.name + ".dat"))
     shutil.copyfile(cp.dat_path, d / (cp.name + "_loop.dat"))
     names.write_text("".join("%s %d\n" % (n, sz) for n, _, sz in cp.flat.inputs))
-    for target in ("circuit", "loop"):
-        subprocess.run(["make", "-C", str(ROOT), target, "PRIME=" + prime, "NAME=" + cp.name, "REF=" + str(REF_ROOT)],
-                       check=True, capture_output=True)
-    fp_file.write_text(fp + "\n")
+    name = cp.name
+
+    def compile_():
+        for target in ("circuit", "loop"):
+            subprocess.run(["make", "-C", str(ROOT), target, "PRIME=" + prime, "NAME=" + name, "REF=" + str(REF_ROOT)],
+                           check=True, capture_output=True)
+        fp_file.write_text(fp + "\n")
+    if later is None:
+        compile_()
+    else:
+        later.append((prime, compile_))
     return cli, loop
 
 
@@ -303,6 +312,7 @@ def build_default_circuits():
     from circom_amd.circuits.basic import Multiplier2
     from circom_amd.circuits.poseidon import Poseidon
     d = _t.mkdtemp(prefix="cw_refbuild_")
+    jobs = []               # the circuits' compilations: emitted one after the other (Python), compiled side by side (g++)
     from circom_amd.circuits.sha256 import Sha256
     from circom_amd.circuits.eddsa import SemaphoreStyle
     from circom_amd.circuits.bigint import BigMultModP
@@ -313,10 +323,21 @@ def build_default_circuits():
                        ("sha256_2048", Program(Sha256(2048)))):
         # (only the flat circuit and the .dat are needed here: one strand variant, no emitted code)
         cp = compile_program(prog, d, name, sym=False, strands=(1,), jit=False, fpjit=False)
-        build_circuit(cp)
+        build_circuit(cp, later=jobs)
     # BASELINE config 5's verifier (2.47 M signals: half a minute of tracing, minutes of g++): parity + CPU baseline of its bench line
     # (only the flat program and its .dat: build_circuit compares fingerprints and returns when the binary is current)
-    build_circuit(_flat_only(bench.make_program("ecdsa_verify"), d, "ecdsa_verify"))
+    build_circuit(_flat_only(bench.make_program("ecdsa_verify"), d, "ecdsa_verify"), later=jobs)
+    if jobs:
+        import concurrent.futures as cf
+        # what the circuits of one prime share (the field library and runtime of `ref`, the renamed main.cpp, the loop driver)
+        # first, once: no two makes write one file
+        for prime in sorted({p_ for p_, _ in jobs}):
+            subprocess.run(["make", "-C", str(ROOT), "ref", "_ref/%s/main_lib.o" % prime, "_ref/%s/ref_loop.o" % prime, "PRIME=" + prime,
+                            "REF=" + str(REF_ROOT)], check=True, capture_output=True)
+        # at most four at a time: g++ -O3 on the 10 MB source of a million-signal circuit holds gigabytes
+        with cf.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), host_cores()[0], 4))) as ex:
+            for f_ in [ex.submit(j_) for _, j_ in jobs]:
+                f_.result()
     # the reference's 64-bit runtime for `bench.py --workload poseidon2_goldilocks` (parity + CPU baseline of that line)
     from circom_amd.frontend.flatten import flatten
     if not (ref_dir("goldilocks") / "poseidon2").exists():
