@@ -19,6 +19,7 @@
 #include "cw_kernels.h"
 #include "cw_r1cs_plan.h"
 #include "cw_bits_host.h"
+#include "cw_devbuf.h"
 
 typedef unsigned __int128 u128;
 
@@ -174,6 +175,16 @@ static bool prime_supported(const U256 &q) {
     return bits >= 225 && bits <= 256 && (q.w[0] & 1);
 }
 
+// a 256-bit value as 9 x 29-bit limbs, the form the device multiplier consumes
+static void limbs29(const uint64_t w[4], uint32_t out[9]) {
+    for (int k = 0; k < 9; k++) {
+        unsigned bit = 29 * k, wi = bit / 64, sh = bit % 64;
+        uint64_t v = w[wi] >> sh;
+        if (sh > 35 && wi + 1 < 4) v |= w[wi + 1] << (64 - sh);
+        out[k] = (uint32_t)(v & 0x1FFFFFFFu);
+    }
+}
+
 static FpParams make_params(const U256 &q) {
     FpParams P;
     memset(&P, 0, sizeof(P));
@@ -190,15 +201,8 @@ static FpParams make_params(const U256 &q) {
     uint32_t q0 = (uint32_t)q.w[0], inv = 1;
     for (int i = 0; i < 5; i++) inv *= 2 - q0 * inv;
     P.np29 = (uint32_t)(0u - inv) & 0x1FFFFFFFu;
-    for (int k = 0; k < 9; k++) {
-        unsigned bit = 29 * k, w = bit / 64, sh = bit % 64;
-        uint64_t v = q.w[w] >> sh;
-        if (sh > 35 && w + 1 < 4) v |= q.w[w + 1] << (64 - sh);
-        P.q29[k] = (uint32_t)(v & 0x1FFFFFFFu);
-        uint64_t v2 = r2.w[w] >> sh;
-        if (sh > 35 && w + 1 < 4) v2 |= r2.w[w + 1] << (64 - sh);
-        P.r2_29[k] = (uint32_t)(v2 & 0x1FFFFFFFu);
-    }
+    limbs29(q.w, P.q29);
+    limbs29(r2.w, P.r2_29);
     P.qbits = u256_bits(q);
     unsigned topbits = P.qbits - 224;             // bits used in the top 32-bit limb
     P.topmask = topbits >= 32 ? 0xFFFFFFFFu : ((1u << topbits) - 1);
@@ -237,6 +241,22 @@ struct FpJit {
     uint32_t r1cs_crc = 0, r1cs_len = 0;                             // the .r1cs constraint section `covered` refers to (0, 0: unknown)
 };
 constexpr const char *FPJIT_KERNEL = "cw_fp_jit";
+
+// `kernel` of an emitted code object on `device`: the module is loaded when a device first asks for it and remembered in `mods`
+static hipError_t module_for_device(std::map<int, std::pair<hipModule_t, hipFunction_t>> &mods, int device, const std::vector<uint8_t> &code,
+                                    const char *kernel, hipFunction_t *fn) {
+    auto it = mods.find(device);
+    if (it == mods.end()) {
+        hipModule_t mod = nullptr;
+        hipFunction_t f = nullptr;
+        hipError_t e = hipModuleLoadData(&mod, code.data());
+        if (e == hipSuccess && (e = hipModuleGetFunction(&f, mod, kernel)) != hipSuccess) hipModuleUnload(mod);
+        if (e != hipSuccess) return e;
+        it = mods.emplace(device, std::make_pair(mod, f)).first;
+    }
+    *fn = it->second.second;
+    return hipSuccess;
+}
 
 // CRC-32 (IEEE, zlib's) of the constraint section of a .r1cs: the identity of the constraint system emitted checks were built
 // from (hip_elements/writers.py write_r1cs returns it, write_tape stores it)
@@ -695,14 +715,9 @@ static int load_tape(cw_circuit *c, const char *path) {
     // D_DOTC constants: kept as 9 x 29-bit limbs (+3 pad words = 48 B per entry, 16-byte aligned for scalar loads)
     c->lconsts.assign((size_t)std::max<uint32_t>(n_lconsts, 1) * 12, 0);
     for (uint32_t k = 0; k < n_lconsts; k++) {
-        uint64_t w[5] = {0, 0, 0, 0, 0};
+        uint64_t w[4];
         memcpy(w, b.data() + off + (size_t)k * 32, 32);
-        for (int l = 0; l < 9; l++) {
-            unsigned bit = 29 * l, wi = bit / 64, sh = bit % 64;
-            uint64_t v = w[wi] >> sh;
-            if (sh > 35) v |= w[wi + 1] << (64 - sh);
-            c->lconsts[(size_t)k * 12 + l] = (uint32_t)(v & 0x1FFFFFFFu);
-        }
+        limbs29(w, &c->lconsts[(size_t)k * 12]);
     }
     off += (size_t)n_lconsts * 32;
     c->w2s.resize(c->n_witness);
@@ -1640,25 +1655,24 @@ struct cw_batch {
     int device = 0;
     uint32_t batch = 0, Bp = 0, lanes = 64, prio_mask = 0;
     hipStream_t stream = nullptr;
-    void *d_V = nullptr;
+    DevBuf<void> d_V;
     size_t v_bytes = 0;
-    CwDRow *d_rows = nullptr;
+    DevBuf<CwDRow> d_rows;
     const Variant *var = nullptr;
-    uint32_t *d_stream_off = nullptr, *d_extra_off = nullptr;
-    uint64_t *d_extras = nullptr, *d_terms = nullptr;
-    uint32_t *d_term_off = nullptr;
-    uint32_t *d_prows = nullptr, *d_ploads = nullptr;   // pipelined variant: device rows (CwPRow) and load lists
-    uint32_t *d_lconsts = nullptr;
-    uint32_t *d_fncode = nullptr, *d_fntab = nullptr;   // circom functions (D_CALL)
-    uint32_t *d_consts = nullptr, *d_w2s = nullptr, *d_status = nullptr, *d_first_bad = nullptr;
+    DevBuf<uint32_t> d_stream_off, d_extra_off;
+    DevBuf<uint64_t> d_extras, d_terms;
+    DevBuf<uint32_t> d_term_off;
+    DevBuf<uint32_t> d_prows, d_ploads;                 // pipelined variant: device rows (CwPRow) and load lists
+    DevBuf<uint32_t> d_lconsts;
+    DevBuf<uint32_t> d_fncode, d_fntab;                 // circom functions (D_CALL)
+    DevBuf<uint32_t> d_consts, d_w2s, d_status, d_first_bad;
     // R1CS check plan (cw_r1cs_plan.h) on the device; r1_entries != 0 selects the LDS-staged kernel
-    uint32_t *d_rctab = nullptr, *d_rctab29 = nullptr, *d_pchunk = nullptr, *d_prec = nullptr, *d_pterms = nullptr, *d_prow = nullptr;
+    DevBuf<uint32_t> d_rctab, d_rctab29, d_pchunk, d_prec, d_pterms, d_prow;
     uint32_t r1_chunks = 0, r1_entries = 0;
-    void *d_in = nullptr;          // AoS staging [batch][n_in][32]
-    void *d_pmask = nullptr;       // cw_set_inputs_bits: the caller's packed masks on the device (8 bytes per input and group)
-    void *d_gather = nullptr;      // [n_witness][32]
-    void *d_bulk = nullptr;        // staging of cw_get_witnesses: [bulk_rows][n_witness][32]
-    uint32_t bulk_rows = 0;
+    DevBuf<void> d_in;             // AoS staging [batch][n_in][32]
+    DevBuf<void> d_pmask;          // cw_set_inputs_bits: the caller's packed masks on the device (8 bytes per input and group)
+    DevBuf<void> d_gather;         // [n_witness][32]
+    DevBuf<void> d_bulk;           // staging of cw_get_witnesses: [rows][n_witness][32], grown to the largest piece asked for
     const void *ext_in = nullptr;  // caller-owned device inputs (cw_set_inputs_device)
     // cw_run_check: cw_run + cw_check_r1cs captured once as a HIP graph and replayed (one launch per step instead of ~10)
     hipGraphExec_t rc_graph = nullptr;
@@ -1680,16 +1694,15 @@ struct cw_batch {
     bool all_set = false, host_dirty = false, ran = false;
     // ---- bit-plane mode (cw_bits.hip): one bit per signal per instance instead of a 32-byte slot ----
     bool bitmode = false;
-    uint64_t *d_T = nullptr, *d_fbmask = nullptr;   // bit table [groups][slots]; per-group mask of instances to re-run wide
+    DevBuf<uint64_t> d_T, d_fbmask;                 // bit table [groups][slots]; per-group mask of instances to re-run wide
     uint64_t t_bytes = 0;
     uint32_t n_groups = 0;
-    uint32_t *d_brecs = nullptr, *d_bcmds = nullptr, *d_aslots = nullptr;   // the gate program: records, command blocks, assertion slots
-    uint32_t *d_wslot = nullptr;                      // witness position -> bit-table slot (sig_slot o w2s)
-    uint32_t *d_fbinst = nullptr;                     // instances of the side batch (device copy of fb_inst)
-    uint32_t fbinst_cap = 0;
+    DevBuf<uint32_t> d_brecs, d_bcmds, d_aslots;    // the gate program: records, command blocks, assertion slots
+    DevBuf<uint32_t> d_wslot;                         // witness position -> bit-table slot (sig_slot o w2s)
+    DevBuf<uint32_t> d_fbinst;                        // instances of the side batch (device copy of fb_inst)
     const void *packed_in = nullptr;                  // cw_set_inputs_bits_device: uint64 masks [groups][n_inputs] instead of ext_in
-    uint32_t *d_erecs = nullptr, *d_wchunk = nullptr, *d_wterms = nullptr, *d_wctab = nullptr, *d_wrow = nullptr;
-    uint32_t *d_ichunk = nullptr, *d_iterms = nullptr, *d_itab = nullptr, *d_irow = nullptr, *d_sigslot = nullptr;
+    DevBuf<uint32_t> d_erecs, d_wchunk, d_wterms, d_wctab, d_wrow;
+    DevBuf<uint32_t> d_ichunk, d_iterms, d_itab, d_irow, d_sigslot;
     uint32_t n_ichunks = 0;
     uint32_t n_evrows = 0, n_wchunks = 0, bits_steps = 0, bits_width = 64;
     // instances whose inputs are not all 0/1 (or that tripped an assertion gate) are re-run by the 256-bit schedule
@@ -1707,9 +1720,9 @@ struct cw_batch {
     bool jit = false, table_dirty = false;             // emitted code runs this batch; the caller holds a raw pointer to the table
     hipFunction_t jit_fn = nullptr;
     // 64-bit runtime: V64[slot][Bp], its program and R1CS terms
-    uint64_t *d_V64 = nullptr, *d_consts64 = nullptr;
-    uint32_t *d_rows64 = nullptr, *d_terms64 = nullptr, *d_chunks64 = nullptr;
-    uint64_t *d_r1flag = nullptr;                      // per group: instances whose fused R1CS check fired (emitted code)
+    DevBuf<uint64_t> d_V64, d_consts64;
+    DevBuf<uint32_t> d_rows64, d_terms64, d_chunks64;
+    DevBuf<uint64_t> d_r1flag;                         // per group: instances whose fused R1CS check fired (emitted code)
     // cw_batch_set_timing: events on the batch's stream around the parts of cw_run / cw_check_r1cs (their own intervals, measured
     // where they run - bench.py's roofline figures): 0 run begins | 1 inputs ingested | 2 evaluation done | 3 check begins | 4 check done
     // cw_batch_set_timing(b, 2) keeps the marks of the last CW_TIMING_RING runs (a new set per cw_run): cw_batch_kernel_ms_mean
@@ -1735,42 +1748,29 @@ static inline void cw_tmark(cw_batch *b, int k) {
 #define TMARK(b, k) cw_tmark((b), (k))
 
 template <typename T>
-static hipError_t upload(T **dst, const std::vector<T> &src, hipStream_t s) {
+static hipError_t upload(DevBuf<T> *dst, const std::vector<T> &src, hipStream_t s) {
     size_t n = std::max<size_t>(src.size(), 1) * sizeof(T);
-    hipError_t e = hipMalloc((void **)dst, n);
+    hipError_t e = dst->alloc(n);
     if (e != hipSuccess) return e;
     if (!src.empty()) e = hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s);
     return e;
 }
 
+// The stream is drained first: a replay of the captured graph may be in flight until then, and it uses the graph exec and
+// every table of the batch.  The d_* members free themselves when the batch is deleted.
 extern "C" void cw_batch_free(cw_batch *b) {
     if (!b) return;
-    if (b->rc_graph) hipGraphExecDestroy(b->rc_graph);
-    b->rc_graph = nullptr;
-    if (b->rc_stream) hipStreamDestroy(b->rc_stream);
-    b->rc_stream = nullptr;
     if (b->c) b->c->live_batches--;
-    if (b->device < 0) {
-        delete b;
-        return;
+    if (b->device >= 0) {
+        hipSetDevice(b->device);
+        hipStreamSynchronize(b->stream);
     }
-    hipSetDevice(b->device);
-    hipStreamSynchronize(b->stream);
+    if (b->rc_graph) hipGraphExecDestroy(b->rc_graph);
+    if (b->rc_stream) hipStreamDestroy(b->rc_stream);
     for (cw_batch::TSet &t : b->tring)
         for (hipEvent_t e : t.ev)
             if (e) hipEventDestroy(e);
     if (b->fb) cw_batch_free(b->fb);
-    void *bptrs[] = {b->d_V64, b->d_consts64, b->d_rows64, b->d_terms64, b->d_chunks64, b->d_T, b->d_fbmask, b->d_r1flag, b->d_brecs, b->d_bcmds, b->d_aslots, b->d_wslot, b->d_fbinst, b->d_erecs, b->d_wchunk, b->d_wterms, b->d_wctab, b->d_wrow,
-                     b->d_ichunk, b->d_iterms, b->d_itab, b->d_irow, b->d_sigslot, b->d_pmask};
-    for (void *p : bptrs)
-        if (p) hipFree(p);
-    if (b->d_fncode) hipFree(b->d_fncode);
-    if (b->d_fntab) hipFree(b->d_fntab);
-    void *ptrs[] = {b->d_V, b->d_prows, b->d_ploads, b->d_rows, b->d_stream_off, b->d_extras, b->d_extra_off, b->d_terms, b->d_term_off, b->d_lconsts, b->d_consts, b->d_w2s, b->d_status, b->d_first_bad,
-                    b->d_rctab, b->d_rctab29, b->d_pchunk, b->d_prec, b->d_pterms, b->d_prow,
-                    b->d_in, b->d_gather, b->d_bulk};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
     delete b;
 }
 
@@ -1780,9 +1780,348 @@ static int batch_setup64(cw_batch *b);
 static int ensure_d_in(cw_batch *b) {
     if (b->d_in) return CW_OK;
     const size_t n = std::max<size_t>((size_t)b->batch * b->c->n_inputs * 32, 32);
-    hipError_t e = hipMalloc(&b->d_in, n);
+    hipError_t e = b->d_in.alloc(n);
     if (e != hipSuccess)
         return fail(CW_EDEVICE, "hipMalloc of the input staging image failed (" + std::to_string(n) + " bytes): " + hipGetErrorString(e));
+    return CW_OK;
+}
+
+// pick the schedule variant.  Up to 8192 waves (two rounds of the chip's 4096 wave slots) a variant with more
+// strands that carry work shortens the critical path of every instance group; a variant whose extra strands
+// only wait at barriers (Poseidon(2) has 3 independent lanes: S = 16 is S = 4 plus 12 idle waves) just takes
+// wave slots.  Measured on Poseidon(2): 512 groups S = 4: 0.81 ms, S = 16: 1.39 ms; 2048 groups S = 4: 2.12 ms,
+// S = 1: 2.53 ms; 4096 groups: S = 1 wins.  CW_STRANDS overrides.
+static const Variant *pick_variant(const cw_circuit *c, uint32_t batch) {
+    uint64_t groups = (batch + 63) / 64;
+    const Variant *best = nullptr;
+    double work1 = 0;                              // circuits with functions: the single strand's time (any variant's work is the same rows)
+    for (auto &v : c->variants)
+        if (!v.kind && v.work > 0 && (work1 == 0 || v.n_strands == 1)) work1 = v.work;
+    for (auto &v : c->variants) {
+        if (v.kind) continue;
+        if (groups * v.n_strands > 8192 && v.n_strands > 1) continue;
+        if (v.n_strands > 1 && v.crit > 0 && work1 < 2.0 * v.crit && !getenv("CW_STRANDS")) {
+            bool have1 = false;
+            for (auto &u : c->variants) have1 |= !u.kind && u.n_strands == 1;
+            if (have1) continue;                   // its strands mostly wait for one chain (a call): no shorter than one strand
+        }
+        if (!best || v.n_active > best->n_active || (v.n_active == best->n_active && v.n_strands < best->n_strands))
+            best = &v;
+    }
+    if (!best)
+        for (auto &v : c->variants)
+            if (!v.kind && (!best || v.n_strands < best->n_strands)) best = &v;
+    // A batch that fills every SIMD with ONE strand (>= 1 024 groups) and whose R1CS check can ride in the rows runs the
+    // single-strand emitted program with the check fused in: no barriers, no hand-offs, no waiting for the slowest strand -
+    // a lone wave per SIMD issues at one instruction per ~4.5 clocks, and the next batch in flight (another wave per SIMD)
+    // fills the gaps.  Poseidon(2) x 65 536, rows + check: 59-62 M witnesses/s against 52 M with four strands
+    // (tools/fpjit_poseidon_strands.sh, fpjit_poseidon_inflight.sh).  CW_STRANDS / CW_FP_JIT = 0 / CW_FP_FUSED = 0 override.
+    {
+        const char *fj0 = getenv("CW_FP_JIT"), *ff0 = getenv("CW_FP_FUSED");
+        if (best && best->n_strands > 1 && !getenv("CW_STRANDS") && !(fj0 && atoi(fj0) == 0) && !(ff0 && atoi(ff0) == 0) &&
+            c->n_constraints && groups >= 1024) {
+            bool have_code = false;
+            for (auto &fj : c->fpjit)
+                have_code |= fj.n_strands == 1 && !fj.covered.empty() && fj.covered.size() == (c->n_constraints + 31) / 32 &&
+                             (uint64_t)fj.n_covered * 2 >= c->n_constraints;
+            if (have_code)
+                for (auto &v : c->variants)
+                    if (!v.kind && v.n_strands == 1) best = &v;
+        }
+    }
+    if (const char *e = best ? getenv("CW_STRANDS") : nullptr) {
+        uint32_t want = (uint32_t)std::max(1, atoi(e));
+        for (auto &v : c->variants) {
+            if (v.kind) continue;
+            bool better = (v.n_strands <= want && v.n_strands > best->n_strands) ||
+                          (best->n_strands > want && v.n_strands < best->n_strands);
+            if (better) best = &v;
+        }
+    }
+    // The pipelined single-wave variant hides the value-table latency inside ONE wave (LDS ring + load lists a batch
+    // ahead), so it wins wherever the strand variants run at one or two waves per SIMD: up to PIPE_MAX_GROUPS groups
+    // of 64 instances.  Beyond that the plain single-strand schedule has enough waves per SIMD to hide the latency
+    // by itself and needs no LDS.  CW_PIPE = 0 / 1 overrides.
+    {
+        const Variant *pv = nullptr;
+        for (auto &v : c->variants)
+            if (v.kind == 1) pv = &v;
+        bool use = pv && (!best || (groups <= PIPE_MAX_GROUPS && !getenv("CW_STRANDS")));   // CW_STRANDS asks for a strand variant
+        if (const char *e = getenv("CW_PIPE")) use = pv && (atoi(e) != 0 || !best);
+        if (use) best = pv;
+    }
+    return best;
+}
+
+// instances per workgroup: when there are fewer workgroups than CUs (256), a batch is spread over more of them
+// by leaving the upper lanes of the waves idle - never beyond one workgroup per CU, because idle lanes
+// still cost VALU issue (measured on Poseidon(2): 32 lanes are 16 % slower as soon as every CU is busy)
+static uint32_t pick_lanes(uint32_t batch) {
+    uint32_t lanes = 64;
+    while (lanes > 16 && 2 * (((uint64_t)batch + lanes - 1) / lanes) <= 256) lanes >>= 1;
+    if (const char *e = getenv("CW_LANES")) {
+        int v = atoi(e);
+        if (v == 16 || v == 32 || v == 64) lanes = (uint32_t)v;
+    }
+    return lanes;
+}
+
+// the variant's emitted code, when the tape carries it (CW_FP_JIT = 0: interpret the rows instead)
+static FpJit *pick_fp_program(cw_circuit *c, const Variant *best, uint32_t batch, uint32_t lanes) {
+    const char *fe_ = getenv("CW_FP_JIT");
+    if (best->kind != 0 || (fe_ && atoi(fe_) == 0)) return nullptr;
+    // A variant may come in two programs: the rows alone, and the rows with the R1CS check fused in (recomputed behind
+    // the rows that produce the wires).  The fused one does about twice the arithmetic in one launch and saves the
+    // check's pass over the table: it wins where the launch is throughput-bound (4 waves per SIMD and more), the plain
+    // one + the stand-alone check kernel where a batch waits on its dependency chain (measured, evaluation + check:
+    // Poseidon(2) x 65 536, 4 waves per SIMD: 1.64 vs 2.07 ms; Semaphore-style x 8 192, 2 per SIMD: 21.1 vs 18.8 ms; its
+    // 1 024-instance shard: 18.0 vs 14.3 ms).  CW_FP_FUSED = 0 / 1 overrides.
+    const uint64_t waves = ((uint64_t)batch + lanes - 1) / lanes * best->n_strands;
+    bool want_fused = (waves >= 4096 || (best->n_strands == 1 && waves >= 1024)) && c->n_constraints != 0;
+    if (const char *e2 = getenv("CW_FP_FUSED")) want_fused = atoi(e2) != 0;
+    FpJit *pick = nullptr;
+    for (auto &fj : c->fpjit) {
+        if (fj.n_strands != best->n_strands) continue;
+        const bool fused = !fj.covered.empty();
+        if (fused && !(c->n_constraints && fj.covered.size() == (c->n_constraints + 31) / 32)) continue;   // another .r1cs
+        if (fused && !getenv("CW_FP_FUSED") && (uint64_t)fj.n_covered * 2 < c->n_constraints)
+            continue;                       // the code covers a minority of the rows: not worth its steps (unless asked for)
+        if (!pick || fused == want_fused) pick = &fj;
+    }
+    return pick;
+}
+
+// pipelined variant: value-table targets become unified slot numbers (signals, then temps), LDS entries of the terms
+// byte offsets; the row table is padded with 3 NOPs (the kernel reads three rows ahead)
+static void resolve_pipe_rows(uint32_t n_signals, const Variant &v, std::vector<uint32_t> &prow, std::vector<uint32_t> &pl,
+                              std::vector<uint64_t> &dterms) {
+    prow.assign(v.prows.size() + 3 * 8, 0);
+    const size_t nrows = v.prows.size() / 8;
+    auto unify = [&](uint32_t t) { return t == 0xFFFFFFFFu ? t : (t & X_TMP) ? n_signals + (t & 0x3FFFFFFFu) : t; };
+    for (size_t r = 0; r < nrows; r++) {
+        const uint32_t *w = &v.prows[r * 8];
+        uint32_t *o = &prow[r * 8];
+        o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+        o[3] = unify(w[3]); o[4] = unify(w[4]);
+        o[5] = w[5]; o[6] = w[6]; o[7] = 0;
+    }
+    for (int k = 0; k < 3; k++) {
+        uint32_t *o = &prow[(nrows + k) * 8];
+        o[0] = D_NOP; o[1] = 0; o[2] = 0xFFu << 16; o[3] = o[4] = 0xFFFFFFFFu; o[5] = o[6] = o[7] = 0;
+    }
+    pl.assign(v.extras.size(), 0);
+    for (size_t k = 0; k < v.extras.size(); k++) {
+        const uint32_t lw = v.extras[k];
+        pl[k] = lw == 0xFFFFFFFFu ? lw : (lw & 0x40000000u) ? (0x80000000u | (lw & 0x3FFFFFFFu)) : unify(lw);
+    }
+    dterms.assign(v.terms.size() / 2, 0);
+    for (size_t k = 0; k + 3 < v.terms.size(); k += 4) {
+        const uint32_t kw = v.terms[k], kind = kw & 7;
+        dterms[k / 2] = ((uint64_t)kind << 61) | ((uint64_t)v.terms[k + 1] * 2048);
+        dterms[k / 2 + 1] = ((uint64_t)(kw >> 31) << 63) | ((uint64_t)v.terms[k + 3] << 32) | v.terms[k + 2];
+    }
+}
+
+// resolve the schedule for this batch: slot numbers -> byte offsets (CwDRow), streams padded with NOPs.
+// Returns whether the streams hold D_BITS rows.
+static bool resolve_strand_rows(uint32_t n_signals, const Variant &v, uint32_t Bp, uint32_t lanes, std::vector<CwDRow> &drows,
+                                std::vector<uint32_t> &tab, std::vector<uint64_t> &dex, std::vector<uint64_t> &dterms,
+                                std::vector<uint32_t> &stream_begin) {
+    const uint64_t stride = (uint64_t)2 * Bp * 16;               // bytes per value slot
+    // an LDS hand-over slot holds the lanes IN USE (32 bytes each): a workgroup of 16 instances needs 36 KB for 72 slots,
+    // not 144 KB, so that the workgroups of several batches in flight share a CU (bench.py --in-flight)
+    const uint64_t lds_slot = (uint64_t)lanes * 32;
+    auto resolve = [&](uint32_t kind, uint32_t idx) -> uint64_t {
+        switch (kind) {
+        case K_SIG: return (uint64_t)idx * stride;
+        case K_TMP: return ((uint64_t)n_signals + idx) * stride;
+        case K_CONST: return (uint64_t)idx * 32;
+        case K_LDS: return (uint64_t)idx * lds_slot;
+        default: return 0;
+        }
+    };
+    drows.clear();
+    std::vector<uint8_t> bits_entry(v.extras.size(), 0);          // extra-destination entries of D_BITS rows
+    drows.reserve(v.rows.size() + 3 * v.n_strands);
+    for (uint32_t st = 0; st < v.n_strands; st++) {
+        size_t sq = v.seq_off[st], xq = v.extra_off[st];
+        for (uint32_t r = v.stream_off[st]; r < v.stream_off[st + 1]; r++) {
+            const CwRow &row = v.rows[r];
+            uint32_t op = row.w0 & 0xFF, dk = (row.w0 >> SH_DK) & 7, ak = (row.w0 >> SH_AK) & 7,
+                     bk = (row.w0 >> SH_BK) & 7;
+            CwDRow d;
+            d.w0 = row.w0;
+            const bool can_fail = op == D_ASSERT_EQ || op == D_ASSERT_NZ || op == D_IDIV || op == D_MOD || op == D_CALL;
+            const uint32_t seq = can_fail ? v.seqs[sq++] : 0;
+            if (op == D_BARRIER) {
+                d.aux = row.dst;
+                d.dst_off = d.a_off = d.b_off = 0;
+            } else if (op == D_LINSUM || op == D_DOTC) {
+                d.aux = row.a;                                   // number of terms
+                d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
+                d.a_off = 0;
+                d.b_off = resolve(bk, row.b);                    // constant term c0 (kind CONST) or nothing
+            } else if (op == D_CALL) {
+                d.aux = row.a;                                   // function id
+                d.dst_off = seq;                                 // reported if the function fails (no destination)
+                d.a_off = 0;
+                d.b_off = resolve(K_TMP, row.b);                 // first register of the call's window
+            } else if (op == D_BIT || op == D_BITS) {
+                d.aux = row.b;                                   // bit index k (D_BITS: of the first bit)
+                d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
+                d.a_off = resolve(ak, row.a);
+                d.b_off = 0;
+                if (op == D_BITS) {                              // its entries carry X_NEXT (bit 29 is not part of their slot number)
+                    const uint32_t nx = (row.w0 >> SH_NX) & 0xFFF;
+                    for (uint32_t e = 0; e < nx; e++) bits_entry[xq + e] = 1;
+                }
+            } else {
+                d.aux = seq;                                     // flat operation, reported in the status word
+                d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
+                d.a_off = resolve(ak, row.a);
+                d.b_off = resolve(bk, row.b);
+            }
+            if (op != D_BARRIER) xq += (row.w0 >> SH_NX) & 0xFFF;
+            drows.push_back(d);
+        }
+        for (int k = 0; k < 3; k++) drows.push_back(CwDRow{D_NOP, 0, 0, 0, 0});
+    }
+    // LINSUM terms: {kind<<61 | byte offset, sign<<63 | |coef|}
+    dterms.assign(v.terms.size() / 2, 0);
+    for (size_t k = 0; k + 3 < v.terms.size(); k += 4) {
+        uint32_t kw = v.terms[k], kind = kw & 7;
+        dterms[k / 2] = ((uint64_t)kind << 61) | resolve(kind, v.terms[k + 1]);
+        // LINSUM: sign | |coef| ; DOTC: index into the limb-form constant table (the kernel multiplies by 48)
+        dterms[k / 2 + 1] = ((uint64_t)(kw >> 31) << 63) | ((uint64_t)v.terms[k + 3] << 32) | v.terms[k + 2];
+    }
+    dex.assign(v.extras.size() + 16, 0);                           // (padded: a D_BITS row reads sixteen entries per trip)
+    for (size_t k = 0; k < v.extras.size(); k++) {
+        uint32_t x = v.extras[k];
+        if (bits_entry[k])
+            dex[k] = ((x & X_NEXT) ? X_NEXT_DEV : 0ull) | ((x & X_TMP) ? 0ull : X_LO_DEV) | resolve((x & X_TMP) ? K_TMP : K_SIG, x & 0x1FFFFFFFu);
+        else if (x & X_LDS) dex[k] = (1ull << 63) | ((uint64_t)(x & 0x3FFFFFFFu) * lds_slot);
+        else dex[k] = resolve((x & X_TMP) ? K_TMP : K_SIG, x & 0x3FFFFFFFu);
+    }
+    // stream offsets now refer to the padded array: every stream is followed by its 3 NOPs ... keep explicit table
+    std::vector<uint32_t> soff(v.n_strands + 1);
+    {
+        uint32_t pos = 0;
+        for (uint32_t st = 0; st < v.n_strands; st++) {
+            soff[st] = pos;
+            pos += (v.stream_off[st + 1] - v.stream_off[st]) + 3;
+        }
+        soff[v.n_strands] = pos;
+    }
+    stream_begin = soff;
+    // the kernel needs [begin, end) of real rows per stream: pass begin in stream_off[s] and end in a second table
+    tab.assign(2 * v.n_strands, 0);
+    for (uint32_t st = 0; st < v.n_strands; st++) {
+        tab[2 * st] = soff[st];
+        tab[2 * st + 1] = soff[st] + (v.stream_off[st + 1] - v.stream_off[st]);
+    }
+    return std::find(bits_entry.begin(), bits_entry.end(), (uint8_t)1) != bits_entry.end();
+}
+
+// the plan of the stand-alone R1CS check (cw_r1cs_plan.h) for this batch, built and uploaded
+static int setup_r1cs_plan(cw_batch *b) {
+    cw_circuit *c = b->c;
+    const char *mode = getenv("CW_R1CS_MODE");
+    cwplan::Plan p;
+    if (mode && !strcmp(mode, "staged")) {
+        uint32_t chunks, entries;
+        r1cs_plan_defaults(b->batch, &chunks, &entries);
+        p = cwplan::build(c->r_ptr, c->r_slot, c->r_coef, c->r_orig, c->n_signals, chunks, entries);
+        HIPCHK(upload(&b->d_prec, p.rec, b->stream));
+        b->r1_entries = p.entries;
+    } else {
+        uint32_t tpc = 192;
+        if (const char *e = getenv("CW_R1CS_TERMS")) tpc = (uint32_t)std::max(8, atoi(e));
+        const bool audit = getenv("CW_R1CS_AUDIT") != nullptr;
+        p = cwplan::build_stream(c->r_ptr, c->r_slot, c->r_coef, c->r_orig, tpc, b->fp_fn && !audit ? b->fp_covered : nullptr,
+                                 getenv("CW_R1CS_NO_BOOL") ? nullptr : &c->r_bool, getenv("CW_R1CS_NO_FOLD") == nullptr);
+    }
+    if (p.chunk.empty()) p.chunk.assign(4, 0);                   // every row is checked by the emitted code: nothing to stream
+    if (p.row_orig.empty()) p.row_orig.assign(1, 0);
+    HIPCHK(upload(&b->d_pchunk, p.chunk, b->stream));
+    HIPCHK(upload(&b->d_pterms, p.terms, b->stream));
+    HIPCHK(upload(&b->d_prow, p.row_orig, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));                        // the plan goes out of scope
+    b->r1_chunks = p.n_chunks;
+    return CW_OK;
+}
+
+// 256-bit engine: the schedule variant and its emitted program, its rows resolved for this batch, the tables on the device
+static int batch_setup256(cw_batch *b) {
+    cw_circuit *c = b->c;
+    const uint32_t batch = b->batch;
+    b->var = pick_variant(c, batch);
+    if (!b->var) return fail(CW_EINVAL, "the tape holds no usable schedule variant");
+    b->lanes = pick_lanes(batch);
+    b->prio_mask = b->var->prio_mask;
+    if (const char *e = getenv("CW_PRIO_MASK")) b->prio_mask = (uint32_t)strtoul(e, nullptr, 0);   // diagnostics
+    if (FpJit *fj = pick_fp_program(c, b->var, batch, b->lanes)) {
+        hipError_t e1 = module_for_device(fj->mod, b->device, fj->code, FPJIT_KERNEL, &b->fp_fn);
+        if (e1 != hipSuccess) return fail(CW_EDEVICE, std::string("loading the emitted 256-bit code failed: ") + hipGetErrorString(e1));
+        b->fp_lds = fj->lds_bytes;
+        if (!fj->covered.empty()) b->fp_covered = &fj->covered;   // findings: second half of d_status (CW_R1CS_AUDIT: re-checked)
+    }
+    size_t slots = (size_t)c->n_signals + b->var->n_tslots;
+    b->v_bytes = slots * 2 * b->Bp * 16;
+    hipError_t e = b->d_V.alloc(b->v_bytes);
+    if (e != hipSuccess)
+        return fail(CW_EDEVICE, "hipMalloc of the value table failed (" + std::to_string(slots) + " slots): " + hipGetErrorString(e));
+    if (b->var->kind == 1) {
+        std::vector<uint32_t> prow, pl;
+        std::vector<uint64_t> dterms;
+        resolve_pipe_rows(c->n_signals, *b->var, prow, pl, dterms);
+        HIPCHK(upload(&b->d_prows, prow, b->stream));
+        HIPCHK(upload(&b->d_ploads, pl, b->stream));
+        HIPCHK(upload(&b->d_terms, dterms, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    } else {
+        const Variant &v = *b->var;
+        std::vector<CwDRow> drows;
+        std::vector<uint32_t> tab;
+        std::vector<uint64_t> dex, dterms;
+        if (resolve_strand_rows(c->n_signals, v, b->Bp, b->lanes, drows, tab, dex, dterms, b->h_stream_begin)) {
+            // D_BITS rows store the lower half of their signal destinations only (cw_tape.h X_LO_DEV): the table starts cleared.
+            // INVARIANT for the life of the batch: nothing else ever writes the upper 16 bytes of such a slot - every writer of
+            // the value table is a row of this schedule (a slot has one producer: lower.py's clobber replay), inputs land in
+            // input slots (never bit destinations), and the bit-plane fallback re-runs whole instances through these same rows
+            if (c->mont) return fail(CW_EIO, "tape: bit-field rows in a schedule of Montgomery-form signals");
+            HIPCHK(hipMemsetAsync(b->d_V, 0, b->v_bytes, b->stream));
+        }
+        HIPCHK(upload(&b->d_rows, drows, b->stream));
+        HIPCHK(upload(&b->d_stream_off, tab, b->stream));
+        HIPCHK(upload(&b->d_extras, dex, b->stream));
+        HIPCHK(upload(&b->d_extra_off, v.extra_off, b->stream));
+        HIPCHK(upload(&b->d_terms, dterms, b->stream));
+        HIPCHK(upload(&b->d_term_off, v.term_off, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));                        // host vectors go out of scope
+    }
+    HIPCHK(upload(&b->d_consts, c->consts, b->stream));
+    HIPCHK(upload(&b->d_fncode, c->fn_code, b->stream));
+    HIPCHK(upload(&b->d_fntab, c->fn_tab, b->stream));
+    HIPCHK(upload(&b->d_lconsts, c->lconsts, b->stream));
+    HIPCHK(upload(&b->d_w2s, c->w2s, b->stream));
+    HIPCHK(b->d_status.alloc((size_t)b->Bp * 4 * 2)); // second half: findings of the emitted code's fused R1CS check
+    HIPCHK(b->d_first_bad.alloc((size_t)b->Bp * 4));
+    if (c->n_constraints) {
+        HIPCHK(upload(&b->d_rctab, c->r_ctab, b->stream));
+        {   // the same coefficients as 9 x 29-bit limbs, the form the multiplier consumes
+            std::vector<uint32_t> t29(c->r_ctab.size() / 8 * 9);
+            for (size_t e = 0; e < c->r_ctab.size() / 8; e++) {
+                uint64_t w[4];
+                memcpy(w, &c->r_ctab[e * 8], 32);
+                limbs29(w, &t29[e * 9]);
+            }
+            HIPCHK(upload(&b->d_rctab29, t29, b->stream));
+        }
+        if (int rc = setup_r1cs_plan(b)) return rc;
+    }
+    HIPCHK(b->d_in.alloc(std::max<size_t>((size_t)batch * c->n_inputs * 32, 32)));
+    HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
+    HIPCHK(cwk_init(b->stream, b->d_V, b->Bp, b->d_status, b->d_first_bad, c->mont, c->P));
     return CW_OK;
 }
 
@@ -1813,364 +2152,18 @@ static int batch_create_impl(cw_circuit *c, int device, uint32_t batch, void *st
     b->batch = batch;
     b->Bp = (batch + 255) / 256 * 256;
     b->stream = (hipStream_t)stream;
-    if (c->is64) {
-        int rc = batch_setup64(b);
-        if (rc != CW_OK) {
-            cw_batch_free(b);
-            return rc;
-        }
-        b->remaining.assign(batch, c->n_inputs);
-        *out = b;
-        return CW_OK;
-    }
-    if (allow_bits && c->has_bits) {
+    int rc;
+    if (c->is64) rc = batch_setup64(b);
+    else if (allow_bits && c->has_bits) {
         // every signal is a bit: the bit-plane program replaces the 256-bit schedule (which stays in the file for the
         // instances whose inputs turn out not to be 0/1)
         b->bitmode = true;
-        int rc = bits_batch_setup(b);
-        if (rc != CW_OK) {
-            cw_batch_free(b);
-            return rc;
-        }
-        b->remaining.assign(batch, c->n_inputs);
-        *out = b;
-        return CW_OK;
+        rc = bits_batch_setup(b);
+    } else rc = batch_setup256(b);
+    if (rc != CW_OK) {              // whatever the engine had allocated goes with the batch, and the circuit's count is put right
+        cw_batch_free(b);
+        return rc;
     }
-    // pick the schedule variant.  Up to 8192 waves (two rounds of the chip's 4096 wave slots) a variant with more
-    // strands that carry work shortens the critical path of every instance group; a variant whose extra strands
-    // only wait at barriers (Poseidon(2) has 3 independent lanes: S = 16 is S = 4 plus 12 idle waves) just takes
-    // wave slots.  Measured on Poseidon(2): 512 groups S = 4: 0.81 ms, S = 16: 1.39 ms; 2048 groups S = 4: 2.12 ms,
-    // S = 1: 2.53 ms; 4096 groups: S = 1 wins.  CW_STRANDS overrides.
-    {
-        uint64_t groups = (batch + 63) / 64;
-        const Variant *best = nullptr;
-        double work1 = 0;                              // circuits with functions: the single strand's time (any variant's work is the same rows)
-        for (auto &v : c->variants)
-            if (!v.kind && v.work > 0 && (work1 == 0 || v.n_strands == 1)) work1 = v.work;
-        for (auto &v : c->variants) {
-            if (v.kind) continue;
-            if (groups * v.n_strands > 8192 && v.n_strands > 1) continue;
-            if (v.n_strands > 1 && v.crit > 0 && work1 < 2.0 * v.crit && !getenv("CW_STRANDS")) {
-                bool have1 = false;
-                for (auto &u : c->variants) have1 |= !u.kind && u.n_strands == 1;
-                if (have1) continue;                   // its strands mostly wait for one chain (a call): no shorter than one strand
-            }
-            if (!best || v.n_active > best->n_active || (v.n_active == best->n_active && v.n_strands < best->n_strands))
-                best = &v;
-        }
-        if (!best)
-            for (auto &v : c->variants)
-                if (!v.kind && (!best || v.n_strands < best->n_strands)) best = &v;
-        // A batch that fills every SIMD with ONE strand (>= 1 024 groups) and whose R1CS check can ride in the rows runs the
-        // single-strand emitted program with the check fused in: no barriers, no hand-offs, no waiting for the slowest strand -
-        // a lone wave per SIMD issues at one instruction per ~4.5 clocks, and the next batch in flight (another wave per SIMD)
-        // fills the gaps.  Poseidon(2) x 65 536, rows + check: 59-62 M witnesses/s against 52 M with four strands
-        // (tools/fpjit_poseidon_strands.sh, fpjit_poseidon_inflight.sh).  CW_STRANDS / CW_FP_JIT = 0 / CW_FP_FUSED = 0 override.
-        {
-            const char *fj0 = getenv("CW_FP_JIT"), *ff0 = getenv("CW_FP_FUSED");
-            if (best && best->n_strands > 1 && !getenv("CW_STRANDS") && !(fj0 && atoi(fj0) == 0) && !(ff0 && atoi(ff0) == 0) &&
-                c->n_constraints && groups >= 1024) {
-                bool have_code = false;
-                for (auto &fj : c->fpjit)
-                    have_code |= fj.n_strands == 1 && !fj.covered.empty() && fj.covered.size() == (c->n_constraints + 31) / 32 &&
-                                 (uint64_t)fj.n_covered * 2 >= c->n_constraints;
-                if (have_code)
-                    for (auto &v : c->variants)
-                        if (!v.kind && v.n_strands == 1) best = &v;
-            }
-        }
-        if (const char *e = best ? getenv("CW_STRANDS") : nullptr) {
-            uint32_t want = (uint32_t)std::max(1, atoi(e));
-            for (auto &v : c->variants) {
-                if (v.kind) continue;
-                bool better = (v.n_strands <= want && v.n_strands > best->n_strands) ||
-                              (best->n_strands > want && v.n_strands < best->n_strands);
-                if (better) best = &v;
-            }
-        }
-        // The pipelined single-wave variant hides the value-table latency inside ONE wave (LDS ring + load lists a batch
-        // ahead), so it wins wherever the strand variants run at one or two waves per SIMD: up to PIPE_MAX_GROUPS groups
-        // of 64 instances.  Beyond that the plain single-strand schedule has enough waves per SIMD to hide the latency
-        // by itself and needs no LDS.  CW_PIPE = 0 / 1 overrides.
-        {
-            const Variant *pv = nullptr;
-            for (auto &v : c->variants)
-                if (v.kind == 1) pv = &v;
-            bool use = pv && (!best || (groups <= PIPE_MAX_GROUPS && !getenv("CW_STRANDS")));   // CW_STRANDS asks for a strand variant
-            if (const char *e = getenv("CW_PIPE")) use = pv && (atoi(e) != 0 || !best);
-            if (use) best = pv;
-        }
-        if (!best) {
-            delete b;
-            return fail(CW_EINVAL, "the tape holds no usable schedule variant");
-        }
-        b->var = best;
-        // instances per workgroup: when there are fewer workgroups than CUs (256), a batch is spread over more of them
-        // by leaving the upper lanes of the waves idle - never beyond one workgroup per CU, because idle lanes
-        // still cost VALU issue (measured on Poseidon(2): 32 lanes are 16 % slower as soon as every CU is busy)
-        uint32_t lanes = 64;
-        while (lanes > 16 && 2 * (((uint64_t)batch + lanes - 1) / lanes) <= 256) lanes >>= 1;
-        if (const char *e = getenv("CW_LANES")) {
-            int v = atoi(e);
-            if (v == 16 || v == 32 || v == 64) lanes = (uint32_t)v;
-        }
-        b->lanes = lanes;
-        b->prio_mask = best->prio_mask;
-        if (const char *e = getenv("CW_PRIO_MASK")) b->prio_mask = (uint32_t)strtoul(e, nullptr, 0);   // diagnostics
-        // the variant's emitted code, when the tape carries it (CW_FP_JIT = 0: interpret the rows instead)
-        const char *fe_ = getenv("CW_FP_JIT");
-        if (best->kind == 0 && !(fe_ && atoi(fe_) == 0)) {
-            // A variant may come in two programs: the rows alone, and the rows with the R1CS check fused in (recomputed behind
-            // the rows that produce the wires).  The fused one does about twice the arithmetic in one launch and saves the
-            // check's pass over the table: it wins where the launch is throughput-bound (4 waves per SIMD and more), the plain
-            // one + the stand-alone check kernel where a batch waits on its dependency chain (measured, evaluation + check:
-            // Poseidon(2) x 65 536, 4 waves per SIMD: 1.64 vs 2.07 ms; Semaphore-style x 8 192, 2 per SIMD: 21.1 vs 18.8 ms; its
-            // 1 024-instance shard: 18.0 vs 14.3 ms).  CW_FP_FUSED = 0 / 1 overrides.
-            const uint64_t waves = ((uint64_t)batch + lanes - 1) / lanes * best->n_strands;
-            bool want_fused = (waves >= 4096 || (best->n_strands == 1 && waves >= 1024)) && c->n_constraints != 0;
-            if (const char *e2 = getenv("CW_FP_FUSED")) want_fused = atoi(e2) != 0;
-            FpJit *pick = nullptr;
-            for (auto &fj : c->fpjit) {
-                if (fj.n_strands != best->n_strands) continue;
-                const bool fused = !fj.covered.empty();
-                if (fused && !(c->n_constraints && fj.covered.size() == (c->n_constraints + 31) / 32)) continue;   // another .r1cs
-                if (fused && !getenv("CW_FP_FUSED") && (uint64_t)fj.n_covered * 2 < c->n_constraints)
-                    continue;                       // the code covers a minority of the rows: not worth its steps (unless asked for)
-                if (!pick || fused == want_fused) pick = &fj;
-            }
-            if (pick) {
-                FpJit &fj = *pick;
-                auto it = fj.mod.find(b->device);
-                if (it == fj.mod.end()) {
-                    hipModule_t mod = nullptr;
-                    hipFunction_t fn = nullptr;
-                    hipError_t e1 = hipModuleLoadData(&mod, fj.code.data());
-                    if (e1 == hipSuccess) e1 = hipModuleGetFunction(&fn, mod, FPJIT_KERNEL);
-                    if (e1 != hipSuccess) {
-                        delete b;
-                        return fail(CW_EDEVICE, std::string("loading the emitted 256-bit code failed: ") + hipGetErrorString(e1));
-                    }
-                    it = fj.mod.emplace(b->device, std::make_pair(mod, fn)).first;
-                }
-                b->fp_fn = it->second.second;
-                b->fp_lds = fj.lds_bytes;
-                if (!fj.covered.empty()) b->fp_covered = &fj.covered;   // findings: second half of d_status (CW_R1CS_AUDIT: re-checked)
-            }
-        }
-    }
-    size_t slots = (size_t)c->n_signals + b->var->n_tslots;
-    b->v_bytes = slots * 2 * b->Bp * 16;
-    hipError_t e = hipMalloc(&b->d_V, b->v_bytes);
-    if (e != hipSuccess) {
-        delete b;
-        return fail(CW_EDEVICE, "hipMalloc of the value table failed (" + std::to_string(slots) + " slots): " +
-                                    hipGetErrorString(e));
-    }
-#define TRY(x)                                                              \
-    do {                                                                    \
-        hipError_t e2 = (x);                                                \
-        if (e2 != hipSuccess) {                                             \
-            cw_batch_free(b);                                               \
-            return fail(CW_EDEVICE, std::string(#x ": ") + hipGetErrorString(e2)); \
-        }                                                                   \
-    } while (0)
-    if (b->var->kind == 1) {
-        // pipelined variant: value-table targets become unified slot numbers (signals, then temps), LDS entries of the terms
-        // byte offsets; the row table is padded with 3 NOPs (the kernel reads three rows ahead)
-        const Variant &v = *b->var;
-        std::vector<uint32_t> prow(v.prows.size() + 3 * 8);
-        const size_t nrows = v.prows.size() / 8;
-        auto unify = [&](uint32_t t) { return t == 0xFFFFFFFFu ? t : (t & X_TMP) ? c->n_signals + (t & 0x3FFFFFFFu) : t; };
-        for (size_t r = 0; r < nrows; r++) {
-            const uint32_t *w = &v.prows[r * 8];
-            uint32_t *o = &prow[r * 8];
-            o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
-            o[3] = unify(w[3]); o[4] = unify(w[4]);
-            o[5] = w[5]; o[6] = w[6]; o[7] = 0;
-        }
-        for (int k = 0; k < 3; k++) {
-            uint32_t *o = &prow[(nrows + k) * 8];
-            o[0] = D_NOP; o[1] = 0; o[2] = 0xFFu << 16; o[3] = o[4] = 0xFFFFFFFFu; o[5] = o[6] = o[7] = 0;
-        }
-        std::vector<uint32_t> pl(v.extras.size());
-        for (size_t k = 0; k < v.extras.size(); k++) {
-            const uint32_t lw = v.extras[k];
-            pl[k] = lw == 0xFFFFFFFFu ? lw : (lw & 0x40000000u) ? (0x80000000u | (lw & 0x3FFFFFFFu)) : unify(lw);
-        }
-        std::vector<uint64_t> dterms(v.terms.size() / 2);
-        for (size_t k = 0; k + 3 < v.terms.size(); k += 4) {
-            const uint32_t kw = v.terms[k], kind = kw & 7;
-            dterms[k / 2] = ((uint64_t)kind << 61) | ((uint64_t)v.terms[k + 1] * 2048);
-            dterms[k / 2 + 1] = ((uint64_t)(kw >> 31) << 63) | ((uint64_t)v.terms[k + 3] << 32) | v.terms[k + 2];
-        }
-        TRY(upload(&b->d_prows, prow, b->stream));
-        TRY(upload(&b->d_ploads, pl, b->stream));
-        TRY(upload(&b->d_terms, dterms, b->stream));
-        TRY(hipStreamSynchronize(b->stream));
-    } else {
-        // resolve the schedule for this batch: slot numbers -> byte offsets (CwDRow), streams padded with NOPs
-        const Variant &v = *b->var;
-        const uint64_t stride = (uint64_t)2 * b->Bp * 16;            // bytes per value slot
-        // an LDS hand-over slot holds the lanes IN USE (32 bytes each): a workgroup of 16 instances needs 36 KB for 72 slots,
-        // not 144 KB, so that the workgroups of several batches in flight share a CU (bench.py --in-flight)
-        const uint64_t lds_slot = (uint64_t)b->lanes * 32;
-        auto resolve = [&](uint32_t kind, uint32_t idx) -> uint64_t {
-            switch (kind) {
-            case K_SIG: return (uint64_t)idx * stride;
-            case K_TMP: return ((uint64_t)c->n_signals + idx) * stride;
-            case K_CONST: return (uint64_t)idx * 32;
-            case K_LDS: return (uint64_t)idx * lds_slot;
-            default: return 0;
-            }
-        };
-        std::vector<CwDRow> drows;
-        std::vector<uint32_t> doff(1, 0);
-        std::vector<uint8_t> bits_entry(v.extras.size(), 0);          // extra-destination entries of D_BITS rows
-        drows.reserve(v.rows.size() + 3 * v.n_strands);
-        for (uint32_t st = 0; st < v.n_strands; st++) {
-            size_t sq = v.seq_off[st], xq = v.extra_off[st];
-            for (uint32_t r = v.stream_off[st]; r < v.stream_off[st + 1]; r++) {
-                const CwRow &row = v.rows[r];
-                uint32_t op = row.w0 & 0xFF, dk = (row.w0 >> SH_DK) & 7, ak = (row.w0 >> SH_AK) & 7,
-                         bk = (row.w0 >> SH_BK) & 7;
-                CwDRow d;
-                d.w0 = row.w0;
-                const bool can_fail = op == D_ASSERT_EQ || op == D_ASSERT_NZ || op == D_IDIV || op == D_MOD || op == D_CALL;
-                const uint32_t seq = can_fail ? v.seqs[sq++] : 0;
-                if (op == D_BARRIER) {
-                    d.aux = row.dst;
-                    d.dst_off = d.a_off = d.b_off = 0;
-                } else if (op == D_LINSUM || op == D_DOTC) {
-                    d.aux = row.a;                                   // number of terms
-                    d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
-                    d.a_off = 0;
-                    d.b_off = resolve(bk, row.b);                    // constant term c0 (kind CONST) or nothing
-                } else if (op == D_CALL) {
-                    d.aux = row.a;                                   // function id
-                    d.dst_off = seq;                                 // reported if the function fails (no destination)
-                    d.a_off = 0;
-                    d.b_off = resolve(K_TMP, row.b);                 // first register of the call's window
-                } else if (op == D_BIT || op == D_BITS) {
-                    d.aux = row.b;                                   // bit index k (D_BITS: of the first bit)
-                    d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
-                    d.a_off = resolve(ak, row.a);
-                    d.b_off = 0;
-                    if (op == D_BITS) {                              // its entries carry X_NEXT (bit 29 is not part of their slot number)
-                        const uint32_t nx = (row.w0 >> SH_NX) & 0xFFF;
-                        for (uint32_t e = 0; e < nx; e++) bits_entry[xq + e] = 1;
-                    }
-                } else {
-                    d.aux = seq;                                     // flat operation, reported in the status word
-                    d.dst_off = dk == KD_NONE ? 0 : resolve(dk, row.dst);
-                    d.a_off = resolve(ak, row.a);
-                    d.b_off = resolve(bk, row.b);
-                }
-                if (op != D_BARRIER) xq += (row.w0 >> SH_NX) & 0xFFF;
-                drows.push_back(d);
-            }
-            doff.push_back((uint32_t)drows.size());
-            for (int k = 0; k < 3; k++) drows.push_back(CwDRow{D_NOP, 0, 0, 0, 0});
-        }
-        // LINSUM terms: {kind<<61 | byte offset, sign<<63 | |coef|}
-        std::vector<uint64_t> dterms(v.terms.size() / 2);
-        for (size_t k = 0; k + 3 < v.terms.size(); k += 4) {
-            uint32_t kw = v.terms[k], kind = kw & 7;
-            dterms[k / 2] = ((uint64_t)kind << 61) | resolve(kind, v.terms[k + 1]);
-            // LINSUM: sign | |coef| ; DOTC: index into the limb-form constant table (the kernel multiplies by 48)
-            dterms[k / 2 + 1] = ((uint64_t)(kw >> 31) << 63) | ((uint64_t)v.terms[k + 3] << 32) | v.terms[k + 2];
-        }
-        std::vector<uint64_t> dex(v.extras.size() + 16, 0);            // (padded: a D_BITS row reads sixteen entries per trip)
-        for (size_t k = 0; k < v.extras.size(); k++) {
-            uint32_t x = v.extras[k];
-            if (bits_entry[k])
-                dex[k] = ((x & X_NEXT) ? X_NEXT_DEV : 0ull) | ((x & X_TMP) ? 0ull : X_LO_DEV) | resolve((x & X_TMP) ? K_TMP : K_SIG, x & 0x1FFFFFFFu);
-            else if (x & X_LDS) dex[k] = (1ull << 63) | ((uint64_t)(x & 0x3FFFFFFFu) * lds_slot);
-            else dex[k] = resolve((x & X_TMP) ? K_TMP : K_SIG, x & 0x3FFFFFFFu);
-        }
-        // stream offsets now refer to the padded array: stream s starts at doff[s] + 3*s ... keep explicit table
-        std::vector<uint32_t> soff(v.n_strands + 1);
-        for (uint32_t st = 0; st <= v.n_strands; st++) soff[st] = 0;
-        {
-            uint32_t pos = 0;
-            for (uint32_t st = 0; st < v.n_strands; st++) {
-                soff[st] = pos;
-                pos += (v.stream_off[st + 1] - v.stream_off[st]) + 3;
-            }
-            soff[v.n_strands] = pos;
-        }
-        b->h_stream_begin = soff;
-        // the kernel needs [begin, end) of real rows per stream: pass begin in stream_off[s] and end in a second table
-        std::vector<uint32_t> tab(2 * v.n_strands);
-        for (uint32_t st = 0; st < v.n_strands; st++) {
-            tab[2 * st] = soff[st];
-            tab[2 * st + 1] = soff[st] + (v.stream_off[st + 1] - v.stream_off[st]);
-        }
-        if (std::find(bits_entry.begin(), bits_entry.end(), (uint8_t)1) != bits_entry.end()) {
-            // D_BITS rows store the lower half of their signal destinations only (cw_tape.h X_LO_DEV): the table starts cleared.
-            // INVARIANT for the life of the batch: nothing else ever writes the upper 16 bytes of such a slot - every writer of
-            // the value table is a row of this schedule (a slot has one producer: lower.py's clobber replay), inputs land in
-            // input slots (never bit destinations), and the bit-plane fallback re-runs whole instances through these same rows
-            if (c->mont) return fail(CW_EIO, "tape: bit-field rows in a schedule of Montgomery-form signals");
-            TRY(hipMemsetAsync(b->d_V, 0, b->v_bytes, b->stream));
-        }
-        TRY(upload(&b->d_rows, drows, b->stream));
-        TRY(upload(&b->d_stream_off, tab, b->stream));
-        TRY(upload(&b->d_extras, dex, b->stream));
-        TRY(upload(&b->d_extra_off, v.extra_off, b->stream));
-        TRY(upload(&b->d_terms, dterms, b->stream));
-        TRY(upload(&b->d_term_off, v.term_off, b->stream));
-        TRY(hipStreamSynchronize(b->stream));                        // host vectors go out of scope
-    }
-    TRY(upload(&b->d_consts, c->consts, b->stream));
-    TRY(upload(&b->d_fncode, c->fn_code, b->stream));
-    TRY(upload(&b->d_fntab, c->fn_tab, b->stream));
-    TRY(upload(&b->d_lconsts, c->lconsts, b->stream));
-    TRY(upload(&b->d_w2s, c->w2s, b->stream));
-    TRY(hipMalloc((void **)&b->d_status, (size_t)b->Bp * 4 * 2));      // second half: findings of the emitted code's fused R1CS check
-    TRY(hipMalloc((void **)&b->d_first_bad, (size_t)b->Bp * 4));
-    if (c->n_constraints) {
-        TRY(upload(&b->d_rctab, c->r_ctab, b->stream));
-        {   // the same coefficients as 9 x 29-bit limbs, the form the multiplier consumes
-            std::vector<uint32_t> t29(c->r_ctab.size() / 8 * 9);
-            for (size_t e = 0; e < c->r_ctab.size() / 8; e++) {
-                uint64_t w[4];
-                memcpy(w, &c->r_ctab[e * 8], 32);
-                for (int k = 0; k < 9; k++) {
-                    unsigned bit = 29 * k, wi = bit / 64, sh = bit % 64;
-                    uint64_t v = w[wi] >> sh;
-                    if (sh > 35 && wi + 1 < 4) v |= w[wi + 1] << (64 - sh);
-                    t29[e * 9 + k] = (uint32_t)(v & 0x1FFFFFFFu);
-                }
-            }
-            TRY(upload(&b->d_rctab29, t29, b->stream));
-        }
-        const char *mode = getenv("CW_R1CS_MODE");
-        cwplan::Plan p;
-        if (mode && !strcmp(mode, "staged")) {
-            uint32_t chunks, entries;
-            r1cs_plan_defaults(batch, &chunks, &entries);
-            p = cwplan::build(c->r_ptr, c->r_slot, c->r_coef, c->r_orig, c->n_signals, chunks, entries);
-            TRY(upload(&b->d_prec, p.rec, b->stream));
-            b->r1_entries = p.entries;
-        } else {
-            uint32_t tpc = 192;
-            if (const char *e = getenv("CW_R1CS_TERMS")) tpc = (uint32_t)std::max(8, atoi(e));
-            const bool audit = getenv("CW_R1CS_AUDIT") != nullptr;
-            p = cwplan::build_stream(c->r_ptr, c->r_slot, c->r_coef, c->r_orig, tpc, b->fp_fn && !audit ? b->fp_covered : nullptr,
-                                     getenv("CW_R1CS_NO_BOOL") ? nullptr : &c->r_bool, getenv("CW_R1CS_NO_FOLD") == nullptr);
-        }
-        if (p.chunk.empty()) p.chunk.assign(4, 0);                   // every row is checked by the emitted code: nothing to stream
-        if (p.row_orig.empty()) p.row_orig.assign(1, 0);
-        TRY(upload(&b->d_pchunk, p.chunk, b->stream));
-        TRY(upload(&b->d_pterms, p.terms, b->stream));
-        TRY(upload(&b->d_prow, p.row_orig, b->stream));
-        TRY(hipStreamSynchronize(b->stream));                        // the plan goes out of scope
-        b->r1_chunks = p.n_chunks;
-    }
-    TRY(hipMalloc(&b->d_in, std::max<size_t>((size_t)batch * c->n_inputs * 32, 32)));
-    TRY(hipMalloc(&b->d_gather, std::max<size_t>((size_t)c->n_witness * 32, 32)));
-    TRY(cwk_init(b->stream, b->d_V, b->Bp, b->d_status, b->d_first_bad, c->mont, c->P));
-#undef TRY
     b->remaining.assign(batch, c->n_inputs);
     *out = b;
     return CW_OK;
@@ -2316,8 +2309,8 @@ extern "C" int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks) {
     // a buffer of their own: the masks are 1 bit per input and instance, the 32-byte staging image (d_in) 256 times that - 226 GB
     // for 2^18 instances of the 27 008-input SHA-256, which the masks must not need
     const size_t nbytes = std::max<size_t>((size_t)b->n_groups * b->c->n_inputs * 8, 8);
-    if (!b->d_pmask) {
-        hipError_t e = hipMalloc(&b->d_pmask, nbytes);
+    {
+        hipError_t e = b->d_pmask.grow(nbytes);
         if (e != hipSuccess) return fail(CW_EDEVICE, "hipMalloc of the packed input masks failed (" + std::to_string(nbytes) + " bytes): " + hipGetErrorString(e));
     }
     HIPCHK(hipMemcpyAsync(b->d_pmask, masks, nbytes, hipMemcpyHostToDevice, b->stream));
@@ -2533,31 +2526,25 @@ extern "C" int cw_set_inputs_json(cw_batch *b, uint32_t instance, const char *js
 // ---------------------------------------------------------------------------------------------------------
 // bit-plane mode
 // ---------------------------------------------------------------------------------------------------------
-#define BTRY(x)                                                                \
-    do {                                                                       \
-        hipError_t e2 = (x);                                                   \
-        if (e2 != hipSuccess) return fail(CW_EDEVICE, std::string(#x ": ") + hipGetErrorString(e2)); \
-    } while (0)
-
 // 64-bit runtime (cw64.hip): value table [slot][Bp] of uint64, the flat program, the R1CS terms
 static int batch_setup64(cw_batch *b) {
     cw_circuit *c = b->c;
     b->v_bytes = (size_t)c->n_slots64 * b->Bp * 8;
-    hipError_t e = hipMalloc((void **)&b->d_V64, b->v_bytes);
+    hipError_t e = b->d_V64.alloc(b->v_bytes);
     if (e != hipSuccess)
         return fail(CW_EDEVICE, "hipMalloc of the value table failed (" + std::to_string(b->v_bytes) + " bytes): " + hipGetErrorString(e));
-    BTRY(hipMemsetAsync(b->d_V64, 0, b->v_bytes, b->stream));
-    BTRY(upload(&b->d_rows64, c->rows64, b->stream));
-    BTRY(upload(&b->d_consts64, c->consts64, b->stream));
-    BTRY(upload(&b->d_terms64, c->r1_terms64, b->stream));
-    BTRY(upload(&b->d_chunks64, c->r1_chunks64, b->stream));
-    BTRY(upload(&b->d_w2s, c->w2s, b->stream));
-    BTRY(hipMalloc((void **)&b->d_status, (size_t)b->Bp * 4));
-    BTRY(hipMalloc((void **)&b->d_first_bad, (size_t)b->Bp * 4));
-    BTRY(hipMalloc(&b->d_in, std::max<size_t>((size_t)b->batch * c->n_inputs * 32, 32)));
-    BTRY(hipMalloc(&b->d_gather, std::max<size_t>((size_t)c->n_witness * 32, 32)));
-    BTRY(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
-    BTRY(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemsetAsync(b->d_V64, 0, b->v_bytes, b->stream));
+    HIPCHK(upload(&b->d_rows64, c->rows64, b->stream));
+    HIPCHK(upload(&b->d_consts64, c->consts64, b->stream));
+    HIPCHK(upload(&b->d_terms64, c->r1_terms64, b->stream));
+    HIPCHK(upload(&b->d_chunks64, c->r1_chunks64, b->stream));
+    HIPCHK(upload(&b->d_w2s, c->w2s, b->stream));
+    HIPCHK(b->d_status.alloc((size_t)b->Bp * 4));
+    HIPCHK(b->d_first_bad.alloc((size_t)b->Bp * 4));
+    HIPCHK(b->d_in.alloc(std::max<size_t>((size_t)b->batch * c->n_inputs * 32, 32)));
+    HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
+    HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
+    HIPCHK(hipStreamSynchronize(b->stream));
     return CW_OK;
 }
 
@@ -2571,17 +2558,8 @@ static int bits_batch_setup(cw_batch *b) {
     b->jit = c->has_jit && b->batch >= cwbits::JIT_MIN_BATCH;
     if (const char *ev = getenv("CW_BITS_JIT")) b->jit = c->has_jit && atoi(ev) != 0;
     if (b->jit) {
-        auto it = c->jit_mod.find(b->device);
-        if (it == c->jit_mod.end()) {
-            hipModule_t mod = nullptr;
-            hipFunction_t fn = nullptr;
-            hipError_t e1 = hipModuleLoadData(&mod, c->jit.code.data());
-            if (e1 == hipSuccess) e1 = hipModuleGetFunction(&fn, mod, cwbits::JIT_KERNEL);
-            if (e1 != hipSuccess)
-                return fail(CW_EDEVICE, std::string("loading the emitted bit-plane code failed: ") + hipGetErrorString(e1));
-            it = c->jit_mod.emplace(b->device, std::make_pair(mod, fn)).first;
-        }
-        b->jit_fn = it->second.second;
+        hipError_t e1 = module_for_device(c->jit_mod, b->device, c->jit.code, cwbits::JIT_KERNEL, &b->jit_fn);
+        if (e1 != hipSuccess) return fail(CW_EDEVICE, std::string("loading the emitted bit-plane code failed: ") + hipGetErrorString(e1));
         b->bits_slots = c->jit.n_slots;
         b->bits_sh = 5;
         b->bits_sigslot = &c->jit.sig_slot;
@@ -2594,18 +2572,18 @@ static int bits_batch_setup(cw_batch *b) {
     }
     const std::vector<uint32_t> &sig_slot = *b->bits_sigslot;
     b->t_bytes = (uint64_t)b->n_groups_padded * b->bits_slots * 8;
-    hipError_t e = hipMalloc((void **)&b->d_T, b->t_bytes);
+    hipError_t e = b->d_T.alloc(b->t_bytes);
     if (e != hipSuccess)
         return fail(CW_EDEVICE, "hipMalloc of the bit table failed (" + std::to_string(b->t_bytes) + " bytes): " + hipGetErrorString(e));
-    BTRY(hipMalloc((void **)&b->d_fbmask, (size_t)b->n_groups_padded * 8));
-    BTRY(hipMalloc((void **)&b->d_r1flag, (size_t)b->n_groups_padded * 8));
+    HIPCHK(b->d_fbmask.alloc((size_t)b->n_groups_padded * 8));
+    HIPCHK(b->d_r1flag.alloc((size_t)b->n_groups_padded * 8));
     if (!b->jit) {
         std::vector<uint32_t> dev, cmds;
         b->bits_steps = cwbits::device_stream(bp, dev, cmds);
-        BTRY(upload(&b->d_brecs, dev, b->stream));
-        BTRY(upload(&b->d_bcmds, cmds, b->stream));
-        BTRY(upload(&b->d_aslots, bp.assert_slots, b->stream));
-        BTRY(hipStreamSynchronize(b->stream));                       // the vectors go out of scope
+        HIPCHK(upload(&b->d_brecs, dev, b->stream));
+        HIPCHK(upload(&b->d_bcmds, cmds, b->stream));
+        HIPCHK(upload(&b->d_aslots, bp.assert_slots, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));                       // the vectors go out of scope
     }
     // instances per wave: small batches are spread over more CUs by giving every group of 64 instances to 2 or 4
     // independent waves (each evaluates the whole program on its 32 / 16 bits of every mask)
@@ -2614,31 +2592,31 @@ static int bits_batch_setup(cw_batch *b) {
         const int w = atoi(ev);
         if (w == 16 || w == 32 || w == 64) b->bits_width = (uint32_t)w;
     }
-    BTRY(upload(&b->d_w2s, c->w2s, b->stream));
-    BTRY(upload(&b->d_sigslot, sig_slot, b->stream));
+    HIPCHK(upload(&b->d_w2s, c->w2s, b->stream));
+    HIPCHK(upload(&b->d_sigslot, sig_slot, b->stream));
     {
         std::vector<uint32_t> wslot(c->w2s.size());
         for (size_t k = 0; k < wslot.size(); k++) wslot[k] = sig_slot[c->w2s[k]];
-        BTRY(upload(&b->d_wslot, wslot, b->stream));
-        BTRY(hipStreamSynchronize(b->stream));
+        HIPCHK(upload(&b->d_wslot, wslot, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
     }
-    BTRY(hipMalloc((void **)&b->d_status, (size_t)b->Bp * 4));
-    BTRY(hipMalloc((void **)&b->d_first_bad, (size_t)b->Bp * 4));
+    HIPCHK(b->d_status.alloc((size_t)b->Bp * 4));
+    HIPCHK(b->d_first_bad.alloc((size_t)b->Bp * 4));
     if (c->n_constraints) {
         uint32_t tpc = 1024;         // terms per chunk = per wave (measured on Sha256(2048) x 65 536: 256 -> 1.35 ms, 1024 -> 1.26, 4096 -> 1.32)
         if (const char *ev = getenv("CW_R1CS_TERMS")) tpc = (uint32_t)std::max(8, atoi(ev));
         cwbits::R1Plan p = cwbits::build_r1cs(c->r_ptr, c->r_slot, c->r_cc, c->r_cctab, c->r_orig, sig_slot, c->q.w, tpc);
-        BTRY(upload(&b->d_erecs, p.erecs, b->stream));
-        BTRY(upload(&b->d_wchunk, p.chunk, b->stream));
-        BTRY(upload(&b->d_wterms, p.terms, b->stream));
-        BTRY(upload(&b->d_wctab, p.ctab, b->stream));
-        BTRY(upload(&b->d_wrow, p.row_orig, b->stream));
-        BTRY(upload(&b->d_ichunk, p.ichunk, b->stream));
-        BTRY(upload(&b->d_iterms, p.iwords, b->stream));
-        BTRY(upload(&b->d_itab, p.itab, b->stream));
-        BTRY(upload(&b->d_irow, p.irow_orig, b->stream));
+        HIPCHK(upload(&b->d_erecs, p.erecs, b->stream));
+        HIPCHK(upload(&b->d_wchunk, p.chunk, b->stream));
+        HIPCHK(upload(&b->d_wterms, p.terms, b->stream));
+        HIPCHK(upload(&b->d_wctab, p.ctab, b->stream));
+        HIPCHK(upload(&b->d_wrow, p.row_orig, b->stream));
+        HIPCHK(upload(&b->d_ichunk, p.ichunk, b->stream));
+        HIPCHK(upload(&b->d_iterms, p.iwords, b->stream));
+        HIPCHK(upload(&b->d_itab, p.itab, b->stream));
+        HIPCHK(upload(&b->d_irow, p.irow_orig, b->stream));
         b->n_ichunks = p.n_ichunks;
-        BTRY(hipStreamSynchronize(b->stream));                       // the plan goes out of scope
+        HIPCHK(hipStreamSynchronize(b->stream));                       // the plan goes out of scope
         b->n_evrows = p.n_evrows;
         if (getenv("CW_VERBOSE"))
             fprintf(stderr, "[cw] bit-plane R1CS plan: %llu trivial, %llu lut, %llu int (%llu terms in whole 32-bit words, %llu blocks of 8, "
@@ -2651,9 +2629,9 @@ static int bits_batch_setup(cw_batch *b) {
     // the 32-byte staging image (d_in) of a bit-plane batch is allocated when a HOST-side setter first needs it: a caller that
     // hands over device buffers (cw_set_inputs_device / cw_set_inputs_bits_device) never does - 137 GB for 2 M instances of
     // Sha256(2048)
-    BTRY(hipMalloc(&b->d_gather, std::max<size_t>((size_t)c->n_witness * 32, 32)));
-    BTRY(cwk_bits_init(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->n_groups_padded, b->d_fbmask, b->d_r1flag, b->d_status, b->d_first_bad, b->Bp));
-    BTRY(hipStreamSynchronize(b->stream));
+    HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
+    HIPCHK(cwk_bits_init(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->n_groups_padded, b->d_fbmask, b->d_r1flag, b->d_status, b->d_first_bad, b->Bp));
+    HIPCHK(hipStreamSynchronize(b->stream));
     b->fb_index.assign(b->batch, -1);
     return CW_OK;
 }
@@ -2662,11 +2640,11 @@ static int bits_run(cw_batch *b, const void *in) {
     cw_circuit *c = b->c;
     const cwbits::Program &bp = c->bits;
     TMARK(b, 0);
-    BTRY(cwk_bits_init(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->n_groups_padded, b->d_fbmask, b->d_r1flag, b->d_status, b->d_first_bad, b->Bp));
+    HIPCHK(cwk_bits_init(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->n_groups_padded, b->d_fbmask, b->d_r1flag, b->d_status, b->d_first_bad, b->Bp));
     if (b->packed_in)
-        BTRY(cwk_bits_ingest_packed(b->stream, b->packed_in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
+        HIPCHK(cwk_bits_ingest_packed(b->stream, b->packed_in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
     else
-        BTRY(cwk_bits_ingest(b->stream, in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch, b->d_fbmask));
+        HIPCHK(cwk_bits_ingest(b->stream, in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch, b->d_fbmask));
     TMARK(b, 1);
     if (b->jit) {
         // one wave per chunk of 2 048 instances runs the circuit's emitted code: gates on registers, every signal value stored
@@ -2675,10 +2653,10 @@ static int bits_run(cw_batch *b, const void *in) {
         void **cfg = b->jit_cfg;
         cfg[0] = HIP_LAUNCH_PARAM_BUFFER_POINTER; cfg[1] = &b->jit_args; cfg[2] = HIP_LAUNCH_PARAM_BUFFER_SIZE; cfg[3] = &b->jit_args_size;
         cfg[4] = HIP_LAUNCH_PARAM_END;
-        BTRY(hipModuleLaunchKernel(b->jit_fn, b->n_groups_padded / 32, 1, 1, 64, 1, 1, 0, b->stream, nullptr, cfg));
+        HIPCHK(hipModuleLaunchKernel(b->jit_fn, b->n_groups_padded / 32, 1, 1, 64, 1, 1, 0, b->stream, nullptr, cfg));
         b->table_dirty = false;
     } else {
-        BTRY(cwk_bits_eval(b->stream, b->d_brecs, b->d_bcmds, b->bits_steps, bp.ring, bp.cache, b->d_T, bp.n_slots, b->n_groups, b->bits_width,
+        HIPCHK(cwk_bits_eval(b->stream, b->d_brecs, b->d_bcmds, b->bits_steps, bp.ring, bp.cache, b->d_T, bp.n_slots, b->n_groups, b->bits_width,
                            b->d_aslots, (uint32_t)bp.assert_slots.size(), b->d_fbmask));
     }
     TMARK(b, 2);
@@ -2693,9 +2671,9 @@ static int bits_run(cw_batch *b, const void *in) {
 static int bits_resolve(cw_batch *b) {
     if (!b->bitmode || b->resolved || !b->ran) return CW_OK;
     cw_circuit *c = b->c;
-    BTRY(hipStreamSynchronize(b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
     std::vector<uint64_t> m(b->n_groups);
-    BTRY(hipMemcpy(m.data(), b->d_fbmask, (size_t)b->n_groups * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(m.data(), b->d_fbmask, (size_t)b->n_groups * 8, hipMemcpyDeviceToHost));
     b->fb_inst.clear();
     std::fill(b->fb_index.begin(), b->fb_index.end(), -1);
     for (uint32_t g = 0; g < b->n_groups; g++)
@@ -2724,19 +2702,13 @@ static int bits_resolve(cw_batch *b) {
         }
         std::vector<uint32_t> inst(b->fb_inst);
         inst.resize(b->fb->batch, b->fb_inst[0]);
-        if (b->fbinst_cap < inst.size()) {
-            if (b->d_fbinst) hipFree(b->d_fbinst);
-            b->d_fbinst = nullptr;
-            b->fbinst_cap = 0;
-            BTRY(hipMalloc((void **)&b->d_fbinst, inst.size() * 4));
-            b->fbinst_cap = (uint32_t)inst.size();
-        }
-        BTRY(hipMemcpyAsync(b->d_fbinst, inst.data(), inst.size() * 4, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(b->d_fbinst.grow(inst.size() * 4));
+        HIPCHK(hipMemcpyAsync(b->d_fbinst, inst.data(), inst.size() * 4, hipMemcpyHostToDevice, b->stream));
         // one kernel gathers the inputs of the listed instances (from the packed masks or the 32-byte image the caller
         // handed over: that buffer must stay unmodified until the first cw_sync / getter after cw_run, see circom_amd.h)
-        BTRY(cwk_bits_collect_inputs(b->stream, b->packed_in, b->packed_in ? nullptr : (b->ext_in ? b->ext_in : b->d_in), b->d_fbinst,
+        HIPCHK(cwk_bits_collect_inputs(b->stream, b->packed_in, b->packed_in ? nullptr : (b->ext_in ? b->ext_in : b->d_in), b->d_fbinst,
                                      (uint32_t)inst.size(), c->n_inputs, b->fb->d_in));
-        BTRY(hipStreamSynchronize(b->stream));                       // `inst` goes out of scope
+        HIPCHK(hipStreamSynchronize(b->stream));                       // `inst` goes out of scope
         b->fb->ext_in = nullptr;
         b->fb->host_dirty = false;
         b->fb->all_set = true;
@@ -2744,7 +2716,7 @@ static int bits_resolve(cw_batch *b) {
         int rc = cw_run(b->fb);
         if (rc == CW_OK && b->checked && c->n_constraints) rc = cw_check_r1cs(b->fb);
         if (rc != CW_OK) return rc;
-        BTRY(hipStreamSynchronize(b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
     }
     b->resolved = true;
     return CW_OK;
@@ -2922,21 +2894,15 @@ extern "C" int cw_check_r1cs(cw_batch *b) {
             // the audit as emitted code: every constraint recomputed from the table's rows (one coalesced row per wire and wave),
             // flags into the (cleared) R1CS flag array; the general kernels below then only name the first bad row of the
             // instances it flagged
-            auto it = c->jit_audit_mod.find(b->device);
-            if (it == c->jit_audit_mod.end()) {
-                hipModule_t mod = nullptr;
-                hipFunction_t fn = nullptr;
-                hipError_t e1 = hipModuleLoadData(&mod, c->jit.audit_code.data());
-                if (e1 == hipSuccess) e1 = hipModuleGetFunction(&fn, mod, cwbits::JIT_KERNEL);
-                if (e1 != hipSuccess) return fail(CW_EDEVICE, std::string("loading the emitted audit code failed: ") + hipGetErrorString(e1));
-                it = c->jit_audit_mod.emplace(b->device, std::make_pair(mod, fn)).first;
-            }
-            HIPCHK(cwk_fill32(b->stream, (uint32_t *)b->d_r1flag, 0u, (size_t)b->n_groups_padded * 2));
+            hipFunction_t audit_fn = nullptr;
+            hipError_t e1 = module_for_device(c->jit_audit_mod, b->device, c->jit.audit_code, cwbits::JIT_KERNEL, &audit_fn);
+            if (e1 != hipSuccess) return fail(CW_EDEVICE, std::string("loading the emitted audit code failed: ") + hipGetErrorString(e1));
+            HIPCHK(cwk_fill32(b->stream, (uint32_t *)b->d_r1flag.get(), 0u, (size_t)b->n_groups_padded * 2));
             b->audit_args = {b->d_T, b->d_fbmask, b->d_r1flag};
             void **cfg = b->audit_cfg;
             cfg[0] = HIP_LAUNCH_PARAM_BUFFER_POINTER; cfg[1] = &b->audit_args; cfg[2] = HIP_LAUNCH_PARAM_BUFFER_SIZE; cfg[3] = &b->jit_args_size;
             cfg[4] = HIP_LAUNCH_PARAM_END;
-            HIPCHK(hipModuleLaunchKernel(it->second.second, b->n_groups_padded / 32, 1, 1, 64, 1, 1, 0, b->stream, nullptr, cfg));
+            HIPCHK(hipModuleLaunchKernel(audit_fn, b->n_groups_padded / 32, 1, 1, 64, 1, 1, 0, b->stream, nullptr, cfg));
             only = b->d_r1flag;
         }
         HIPCHK(cwk_bits_r1cs(b->stream, b->d_erecs, b->n_evrows, b->d_wchunk, b->n_wchunks, b->d_wterms, b->d_wctab, b->d_wrow,
@@ -3106,13 +3072,7 @@ extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uin
     const size_t row = (size_t)c->n_witness * 32;
     uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
     per = std::max<uint32_t>(64, per / 64 * 64);
-    if (b->bulk_rows < per) {
-        if (b->d_bulk) hipFree(b->d_bulk);
-        b->d_bulk = nullptr;
-        b->bulk_rows = 0;
-        HIPCHK(hipMalloc(&b->d_bulk, (size_t)per * row));
-        b->bulk_rows = per;
-    }
+    HIPCHK(b->d_bulk.grow((size_t)per * row));
     for (uint32_t done = 0; done < count; done += per) {
         const uint32_t n = std::min(per, count - done);
         if (c->is64)
@@ -3213,16 +3173,15 @@ extern "C" int cw_get_public_device(cw_batch *b, void *d_out) {
         if (int rc = bits_resolve(b)) return rc;
         HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + 1, np, 0, b->batch, d_out));
         if (!b->fb_inst.empty()) {
-            void *tmp = nullptr;
+            DevBuf<void> tmp;
             const size_t prow = (size_t)np * 32;
-            HIPCHK(hipMalloc(&tmp, (size_t)b->fb->batch * prow));
+            HIPCHK(tmp.alloc((size_t)b->fb->batch * prow));
             int rc = cw_get_public_device(b->fb, tmp);
             for (size_t k = 0; rc == CW_OK && k < b->fb_inst.size(); k++)
-                if (hipMemcpyAsync((char *)d_out + (size_t)b->fb_inst[k] * prow, (char *)tmp + k * prow, prow, hipMemcpyDeviceToDevice,
+                if (hipMemcpyAsync((char *)d_out + (size_t)b->fb_inst[k] * prow, (char *)tmp.get() + k * prow, prow, hipMemcpyDeviceToDevice,
                                    b->stream) != hipSuccess)
                     rc = fail(CW_EDEVICE, "copy of re-run public signals failed");
-            hipStreamSynchronize(b->stream);
-            hipFree(tmp);
+            hipStreamSynchronize(b->stream);   // the copies read `tmp`
             return rc;
         }
         return CW_OK;
@@ -3239,16 +3198,15 @@ extern "C" int cw_get_public(cw_batch *b, uint8_t *out) {
     NEED_DEVICE(b);
     const size_t bytes = (size_t)b->batch * cw_n_public(b->c) * 32;
     if (bytes == 0) return CW_OK;
-    void *d = nullptr;
+    DevBuf<void> d;
     HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipMalloc(&d, bytes));
+    HIPCHK(d.alloc(bytes));
     int rc = cw_get_public_device(b, d);
     if (rc == CW_OK) {
         hipError_t e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, b->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
         if (e != hipSuccess) rc = fail(CW_EDEVICE, hipGetErrorString(e));
     }
-    hipFree(d);
     return rc;
 }
 
@@ -3275,7 +3233,7 @@ extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint
         out[0] = (uint8_t)((m >> (instance & 63)) & 1);
         return CW_OK;
     }
-    const uint8_t *V = (const uint8_t *)b->d_V;
+    const uint8_t *V = (const uint8_t *)b->d_V.get();
     size_t base = ((size_t)slot * 2 * b->Bp + instance) * 16;
     HIPCHK(hipMemcpyAsync(out, V + base, 16, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipMemcpyAsync(out + 16, V + base + (size_t)b->Bp * 16, 16, hipMemcpyDeviceToHost, b->stream));
@@ -3366,7 +3324,7 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
         std::vector<uint8_t> buf(std::min(total, piece));
         for (size_t at = 0; at < total && ok; at += piece) {
             const size_t n = std::min(piece, total - at);
-            hipError_t e = hipMemcpy(buf.data(), (const uint8_t *)b->d_T + at, n, hipMemcpyDeviceToHost);
+            hipError_t e = hipMemcpy(buf.data(), (const uint8_t *)b->d_T.get() + at, n, hipMemcpyDeviceToHost);
             if (e != hipSuccess) {
                 fclose(f);
                 return fail(CW_EDEVICE, std::string("copying the bit table: ") + hipGetErrorString(e));
@@ -3622,11 +3580,11 @@ extern "C" int cw_bits_eval_bench(int device, uint32_t ring, uint32_t cache, uin
     HIPCHK(hipSetDevice(device));
     std::vector<uint32_t> dev, dcmds;
     const uint32_t steps = cwbits::device_stream(p, dev, dcmds);
-    uint32_t *d_recs = nullptr, *d_cmds = nullptr;
-    void *d_T = nullptr;
+    DevBuf<uint32_t> d_recs, d_cmds;
+    DevBuf<void> d_T;
     HIPCHK(upload(&d_recs, dev, nullptr));
     HIPCHK(upload(&d_cmds, dcmds, nullptr));
-    HIPCHK(hipMalloc(&d_T, (size_t)n_groups * n_slots * 8));
+    HIPCHK(d_T.alloc((size_t)n_groups * n_slots * 8));
     HIPCHK(hipMemset(d_T, 0, (size_t)n_groups * n_slots * 8));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
@@ -3636,9 +3594,9 @@ extern "C" int cw_bits_eval_bench(int device, uint32_t ring, uint32_t cache, uin
     if (getenv("CW_BENCH_COLD")) {
         // every launch behind 6 GB of unrelated writes (what the ingest and check kernels of a real step leave in the
         // caches and TLBs): the launches are timed one by one
-        void *d_junk = nullptr;
+        DevBuf<void> d_junk;
         const size_t junk = (size_t)6 << 30;
-        HIPCHK(hipMalloc(&d_junk, junk));
+        HIPCHK(d_junk.alloc(junk));
         for (uint32_t i = 0; i < iters; i++) {
             HIPCHK(hipMemsetAsync(d_junk, (int)i, junk, nullptr));
             HIPCHK(hipEventRecord(e0, nullptr));
@@ -3649,7 +3607,6 @@ extern "C" int cw_bits_eval_bench(int device, uint32_t ring, uint32_t cache, uin
             HIPCHK(hipEventElapsedTime(&ti, e0, e1));
             t += ti;
         }
-        hipFree(d_junk);
     } else {
         HIPCHK(hipEventRecord(e0, nullptr));
         for (uint32_t i = 0; i < iters; i++)
@@ -3661,9 +3618,6 @@ extern "C" int cw_bits_eval_bench(int device, uint32_t ring, uint32_t cache, uin
     *ms = t / iters;
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(d_recs);
-    hipFree(d_cmds);
-    hipFree(d_T);
     return CW_OK;
 }
 
@@ -3677,11 +3631,11 @@ extern "C" int cw_fp_mul_bench(const uint8_t prime_le32[32], int device, uint32_
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CW_EDEVICE, "no HIP device available");
     HIPCHK(hipSetDevice(device));
     FpParams P = make_params(q);
-    void *da, *db, *dout;
+    DevBuf<void> da, db, dout;
     size_t bytes = (size_t)n * 32;
-    HIPCHK(hipMalloc(&da, bytes));
-    HIPCHK(hipMalloc(&db, bytes));
-    HIPCHK(hipMalloc(&dout, bytes));
+    HIPCHK(da.alloc(bytes));
+    HIPCHK(db.alloc(bytes));
+    HIPCHK(dout.alloc(bytes));
     HIPCHK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
     hipEvent_t e0, e1;
@@ -3698,9 +3652,6 @@ extern "C" int cw_fp_mul_bench(const uint8_t prime_le32[32], int device, uint32_
     HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(da);
-    hipFree(db);
-    hipFree(dout);
     return CW_OK;
 }
 
@@ -3714,14 +3665,14 @@ extern "C" int cw_fp_op(const uint8_t prime_le32[32], int device, uint32_t dop, 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CW_EDEVICE, "no HIP device available");
     HIPCHK(hipSetDevice(device));
     FpParams P = make_params(q);
-    void *da, *db, *dc, *dout;
-    uint32_t *dst;
+    DevBuf<void> da, db, dc, dout;
+    DevBuf<uint32_t> dst;
     size_t bytes = (size_t)n * 32;
-    HIPCHK(hipMalloc(&da, bytes));
-    HIPCHK(hipMalloc(&db, bytes));
-    HIPCHK(hipMalloc(&dc, bytes));
-    HIPCHK(hipMalloc(&dout, bytes));
-    HIPCHK(hipMalloc((void **)&dst, (size_t)n * 4));
+    HIPCHK(da.alloc(bytes));
+    HIPCHK(db.alloc(bytes));
+    HIPCHK(dc.alloc(bytes));
+    HIPCHK(dout.alloc(bytes));
+    HIPCHK(dst.alloc((size_t)n * 4));
     HIPCHK(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dc, c, bytes, hipMemcpyHostToDevice));
@@ -3729,10 +3680,5 @@ extern "C" int cw_fp_op(const uint8_t prime_le32[32], int device, uint32_t dop, 
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost));
-    hipFree(da);
-    hipFree(db);
-    hipFree(dc);
-    hipFree(dout);
-    hipFree(dst);
     return CW_OK;
 }
