@@ -202,6 +202,62 @@ __global__ void __launch_bounds__(256) cw64_gather_kernel(const uint64_t *__rest
     o[1] = o[2] = o[3] = 0;
 }
 
+// Bulk egress as a transpose: `count` instances from `first` as [count][n_wit][EB] bytes, EB = 32 (the boundary's element,
+// value + 24 zero bytes) or 8 (the .wtns element of this runtime: n8 = 8, common64/main.cpp writeBinWitness).  The gather
+// above gives consecutive lanes consecutive ENTRIES: every lane reads another row of V[slot][instance], Bp * 8 bytes from its
+// neighbour's - 64 cache lines for 512 useful bytes.  Here a workgroup of four waves owns 64 instances x EG_T entries:
+//   read    wave w takes the entries k = w, w + 4, ... of the tile; w2s[k] is wave-uniform and the 64 lanes read 64 consecutive
+//           instances of that slot (one 512-byte access, as the evaluation kernel reads its operands); the 16 loads of a wave are
+//           issued before the first value is used
+//   stage   tile[k][j] in LDS with rows of EG_S = 65 words of 8 bytes.  Row-wise write (ds_write_b64: four groups of 16
+//           consecutive lanes, bank = (a/4) % 32): a group writes 16 consecutive words = 32 consecutive dwords, every bank once,
+//           whatever the row's start.  Column-wise read (ds_read_b64: two groups of 32 lanes, bank = (a/4) % 64): lane l reads
+//           word l' * 65 + j with l' = l (8-byte form) or l / 2 (32-byte form, even lanes only), dword 2 (l' * 65 + j), bank
+//           pair 2 ((l' + j) % 32): the 32 (or 16) rows l' of a group fall on distinct pairs.  With rows of 64 words every lane
+//           of a group would hit pair 2 (j % 32): 32-way.  (Odd is what matters: 65 is the smallest odd stride >= 64.)
+//   write   wave w takes the instances j = w, w + 4, ...; consecutive lanes write consecutive pieces of out[j][k0 .. k0 + EG_T):
+//           8-byte form: the 64 values, 512 contiguous bytes (8-byte stores: with n_wit odd a row starts on an 8-byte boundary
+//           only); 32-byte form: 16-byte pieces {value, 0} (even lanes) and {0, 0} (odd lanes), 1 KiB contiguous per store,
+//           two stores per row of the tile.  `out` must be 16-byte aligned in the 32-byte form.
+// Lanes past `count` and entries past n_wit neither read nor write.
+#define EG_T 64
+#define EG_S 65
+template <int EB>
+__global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit,
+                                                          uint32_t Bp, uint32_t first, uint32_t count, uint8_t *__restrict__ out) {
+    __shared__ uint64_t tile[EG_T * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
+    const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
+    const uint64_t *Vj = V + first + j0 + lane;
+    uint64_t v[EG_T / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        const uint32_t k = wave + 4 * i;
+        const uint32_t slot = w2s[k < nk ? k0 + k : k0];             // always an entry of the list: the scalar load needs no branch
+        v[i] = k < nk && lane < nj ? Vj[(size_t)slot * Bp] : 0;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) tile[(wave + 4 * i) * EG_S + lane] = v[i];
+    __syncthreads();
+    for (uint32_t j = wave; j < nj; j += 4) {
+        const size_t at = (size_t)(j0 + j) * n_wit + k0;             // first element of this row of the tile in `out`
+        if (EB == 8) {
+            if (lane < nk) ((uint64_t *)out)[at + lane] = tile[lane * EG_S + j];
+        } else {
+            uint4 *row = (uint4 *)out + at * 2;
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t p = lane + 64 * h, k = p >> 1;
+                if (k < nk) {
+                    const uint64_t x = p & 1u ? 0 : tile[k * EG_S + j];
+                    row[p] = make_uint4((uint32_t)x, (uint32_t)(x >> 32), 0, 0);
+                }
+            }
+        }
+    }
+}
+
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 hipError_t cwk64_init(hipStream_t s, void *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad) {
     hipLaunchKernelGGL(cw64_init_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, (uint64_t *)V, Bp, status, first_bad);
@@ -234,6 +290,24 @@ hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint3
         const uint32_t n = count - done < 65535u ? count - done : 65535u;
         hipLaunchKernelGGL(cw64_gather_kernel, dim3((n_wit + 255) / 256, n), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done,
                            n, (uint64_t *)out + (size_t)done * n_wit * 4);
+    }
+    return hipGetLastError();
+}
+// elem_bytes = 8 or 32; a launch holds at most 65 535 tiles of 64 instances (gridDim.y), larger counts are split as above
+hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                        void *out, uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if (elem_bytes == 32 && ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+    if (!n_wit || !count) return hipSuccess;
+    const uint32_t per = 65535u * 64u;
+    for (uint32_t done = 0; done < count; done += per) {
+        const uint32_t n = count - done < per ? count - done : per;
+        const dim3 grid((n_wit + EG_T - 1) / EG_T, (n + 63) / 64);
+        uint8_t *o = (uint8_t *)out + (size_t)done * n_wit * elem_bytes;
+        if (elem_bytes == 8)
+            hipLaunchKernelGGL(cw64_egress_kernel<8>, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done, n, o);
+        else
+            hipLaunchKernelGGL(cw64_egress_kernel<32>, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done, n, o);
     }
     return hipGetLastError();
 }

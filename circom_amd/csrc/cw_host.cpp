@@ -36,7 +36,7 @@ static int fail(int code, const std::string &msg) {
 
 #define NEED_DEVICE(b) \
     if ((b)->device < 0) return fail(CW_EDEVICE, "host-only batch: no GPU attached (the hot path has no CPU fallback)")
-// entry points the 64-bit runtime (--prime goldilocks, cw64.hip) does not serve yet
+// what the 64-bit runtime (--prime goldilocks, cw64.hip) does not serve: packed boolean inputs
 #define NOT_FOR_64(b, what) \
     if ((b)->c->is64) return fail(CW_ESTATE, what " is not available for circuits of the 64-bit runtime (--prime goldilocks)")
 
@@ -1722,6 +1722,7 @@ struct cw_batch {
     // 64-bit runtime: V64[slot][Bp], its program and R1CS terms
     DevBuf<uint64_t> d_V64, d_consts64;
     DevBuf<uint32_t> d_rows64, d_terms64, d_chunks64;
+    bool egress_tiled = true;                          // CW64_EGRESS_TILED=0: the 32-byte bulk forms go through cw64_gather_kernel (A/B timing)
     DevBuf<uint64_t> d_r1flag;                         // per group: instances whose fused R1CS check fired (emitted code)
     // cw_batch_set_timing: events on the batch's stream around the parts of cw_run / cw_check_r1cs (their own intervals, measured
     // where they run - bench.py's roofline figures): 0 run begins | 1 inputs ingested | 2 evaluation done | 3 check begins | 4 check done
@@ -2543,8 +2544,19 @@ static int batch_setup64(cw_batch *b) {
     HIPCHK(b->d_first_bad.alloc((size_t)b->Bp * 4));
     HIPCHK(b->d_in.alloc(std::max<size_t>((size_t)b->batch * c->n_inputs * 32, 32)));
     HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
+    if (const char *e = getenv("CW64_EGRESS_TILED")) b->egress_tiled = atoi(e) != 0;
     HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
     HIPCHK(hipStreamSynchronize(b->stream));
+    return CW_OK;
+}
+// bulk egress of the 64-bit runtime: [count][n_witness][eb] at d_out, eb = 32 or 8, asynchronous on the batch's stream.  The tiled
+// transpose serves both; its 16-byte stores need an aligned destination, so a 32-byte image at an odd address takes the gather.
+static int egress64(cw_batch *b, uint32_t first, uint32_t count, void *d_out, uint32_t eb) {
+    const cw_circuit *c = b->c;
+    if (eb == 32 && (!b->egress_tiled || ((uintptr_t)d_out & 15)))
+        HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, first, count, d_out));
+    else
+        HIPCHK(cwk64_egress(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, first, count, d_out, eb));
     return CW_OK;
 }
 
@@ -3061,7 +3073,8 @@ extern "C" int cw_get_witness(cw_batch *b, uint32_t instance, uint8_t *out) {
 
 // Bulk form: `count` instances starting at `first`, [count][n_witness][32 B], transposed on the device and
 // copied in pieces of at most 256 MiB through a staging buffer that is allocated on first use.
-extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) {
+// eb = bytes per element in `out`: 32, or cw_element_bytes(c) (8 for the 64-bit runtime: the bodies of its .wtns files).
+static int get_witnesses_host(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out, uint32_t eb) {
     if (!b || !out) return fail(CW_EINVAL, "null argument");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
     NEED_DEVICE(b);
@@ -3069,15 +3082,15 @@ extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uin
     cw_circuit *c = b->c;
     HIPCHK(hipSetDevice(b->device));
     if (int rc = bits_resolve(b)) return rc;
-    const size_t row = (size_t)c->n_witness * 32;
+    const size_t row = (size_t)c->n_witness * eb;
     uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
     per = std::max<uint32_t>(64, per / 64 * 64);
     HIPCHK(b->d_bulk.grow((size_t)per * row));
     for (uint32_t done = 0; done < count; done += per) {
         const uint32_t n = std::min(per, count - done);
-        if (c->is64)
-            HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, first + done, n, b->d_bulk));
-        else if (b->bitmode)
+        if (c->is64) {
+            if (int rc = egress64(b, first + done, n, b->d_bulk, eb)) return rc;
+        } else if (b->bitmode)
             HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot, c->n_witness, first + done, n, b->d_bulk));
         else
             HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, first + done, n, b->d_bulk, c->mont, c->P));
@@ -3095,17 +3108,19 @@ extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uin
         }
     return CW_OK;
 }
+extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) { return get_witnesses_host(b, first, count, out, 32); }
+extern "C" uint32_t cw_element_bytes(const cw_circuit *c) { return c && c->is64 ? 8 : 32; }
 
 // Device-side form for GPU provers: canonical 32-byte values of `count` instances written to DEVICE memory
 // ([count][n_witness][32]); no host copy.  In bit-plane batches this is where a bit becomes a field element again.
 extern "C" int cw_get_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
     if (!b || !d_out) return fail(CW_EINVAL, "null argument");
-    NOT_FOR_64(b, "cw_get_witnesses_device");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
     NEED_DEVICE(b);
     if (!b->ran) return fail(CW_ESTATE, "cw_get_witnesses_device before cw_run");
     cw_circuit *c = b->c;
     HIPCHK(hipSetDevice(b->device));
+    if (c->is64) return egress64(b, first, count, d_out, 32);
     if (!b->bitmode) {
         HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, first, count, d_out, c->mont, c->P));
         return CW_OK;
@@ -3135,6 +3150,18 @@ extern "C" int cw_get_witnesses_device(cw_batch *b, uint32_t first, uint32_t cou
     return CW_OK;
 }
 
+// The same with the element the circuit's .wtns files carry (cw_element_bytes): [count][n_witness][8] for the 64-bit runtime -
+// all a Goldilocks prover reads; three quarters of the 32-byte image are zeros.  Every other circuit: the call above.
+extern "C" int cw_get_witnesses_device_n8(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
+    if (!b || !d_out) return fail(CW_EINVAL, "null argument");
+    if (!b->c->is64) return cw_get_witnesses_device(b, first, count, d_out);
+    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
+    NEED_DEVICE(b);
+    if (!b->ran) return fail(CW_ESTATE, "cw_get_witnesses_device_n8 before cw_run");
+    HIPCHK(hipSetDevice(b->device));
+    return egress64(b, first, count, d_out, 8);
+}
+
 // Chunked device-side egress for provers: the canonical image of `count` instances does not fit anywhere for a
 // million-signal circuit (32 MB per instance), so it is produced `chunk` instances at a time into two caller-owned
 // device buffers in turn; after each chunk's transpose has been ENQUEUED on the batch's stream, `consume` is called with
@@ -3144,7 +3171,6 @@ extern "C" int cw_get_witnesses_device(cw_batch *b, uint32_t first, uint32_t cou
 extern "C" int cw_stream_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, uint32_t chunk, void *d_buf0, void *d_buf1,
                                           cw_chunk_fn consume, void *user) {
     if (!b || !d_buf0 || !d_buf1 || !consume || chunk == 0) return fail(CW_EINVAL, "null argument / zero chunk");
-    NOT_FOR_64(b, "cw_stream_witnesses_device");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
     uint32_t n_chunk = 0;
     for (uint32_t done = 0; done < count; done += chunk, n_chunk++) {
@@ -3291,7 +3317,6 @@ extern "C" int cw_write_wtns(cw_batch *b, uint32_t instance, const char *path) {
 //            that are not 0/1, tripped assertions) carry their field elements
 extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
     if (!b || !path) return fail(CW_EINVAL, "null argument");
-    NOT_FOR_64(b, "cw_write_wtnsb");
     NEED_DEVICE(b);
     if (!b->ran) return fail(CW_ESTATE, "cw_write_wtnsb before cw_run");
     cw_circuit *c = b->c;
@@ -3299,18 +3324,18 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
     if (int rc = bits_resolve(b)) return rc;
     FILE *f = fopen(path, "wb");
     if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
-    const uint32_t version = 1, kind = b->bitmode ? 1u : 0u, n8 = 32, nw = c->n_witness, batch = b->batch;
+    const uint32_t version = 1, kind = b->bitmode ? 1u : 0u, n8 = cw_element_bytes(c), nw = c->n_witness, batch = b->batch;
     bool ok = fwrite("wtnb", 4, 1, f) == 1;
     ok &= fwrite(&version, 4, 1, f) == 1 && fwrite(&kind, 4, 1, f) == 1 && fwrite(&n8, 4, 1, f) == 1;
-    ok &= fwrite(c->q.w, 32, 1, f) == 1 && fwrite(&nw, 4, 1, f) == 1 && fwrite(&batch, 4, 1, f) == 1;
-    const size_t row = (size_t)nw * 32;
+    ok &= fwrite(c->q.w, n8, 1, f) == 1 && fwrite(&nw, 4, 1, f) == 1 && fwrite(&batch, 4, 1, f) == 1;
+    const size_t row = (size_t)nw * n8;
     int rc = CW_OK;
     if (!b->bitmode) {
         const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(batch, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
         std::vector<uint8_t> buf((size_t)per * row);
         for (uint32_t done = 0; done < batch && rc == CW_OK && ok; done += per) {
             const uint32_t n = std::min(per, batch - done);
-            rc = cw_get_witnesses(b, done, n, buf.data());
+            rc = get_witnesses_host(b, done, n, buf.data(), n8);
             if (rc == CW_OK) ok &= fwrite(buf.data(), row, n, f) == n;
         }
     } else {
@@ -3348,7 +3373,6 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
 // `pattern` is a printf pattern with one %u / %d (the instance number).  What a prover farm consumes.
 extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern) {
     if (!b || !pattern) return fail(CW_EINVAL, "null argument");
-    NOT_FOR_64(b, "cw_write_wtns_many");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
     {   // exactly one integer conversion, nothing else
         int convs = 0;
@@ -3363,22 +3387,23 @@ extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, c
         if (convs != 1) return fail(CW_EINVAL, "pattern must hold exactly one %u / %d conversion");
     }
     cw_circuit *c = b->c;
-    const size_t row = (size_t)c->n_witness * 32;
+    const uint32_t eb = cw_element_bytes(c);        // 8 for the 64-bit runtime: its rows leave the device as the files hold them
+    const size_t row = (size_t)c->n_witness * eb;
     const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
     std::vector<uint8_t> buf((size_t)per * row);
     for (uint32_t done = 0; done < count; done += per) {
         const uint32_t n = std::min(per, count - done);
-        int rc = cw_get_witnesses(b, first + done, n, buf.data());
+        int rc = get_witnesses_host(b, first + done, n, buf.data(), eb);
         if (rc) return rc;
         for (uint32_t k = 0; k < n; k++) {
             char path[4096];
             snprintf(path, sizeof path, pattern, first + done + k);
             FILE *f = fopen(path, "wb");
             if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
-            uint32_t version = 2, nsec = 2, id1 = 1, n8 = 32, id2 = 2, nw = c->n_witness;
+            uint32_t version = 2, nsec = 2, id1 = 1, n8 = eb, id2 = 2, nw = c->n_witness;
             uint64_t len1 = 8 + n8, len2 = (uint64_t)n8 * nw;
             fwrite("wtns", 4, 1, f); fwrite(&version, 4, 1, f); fwrite(&nsec, 4, 1, f);
-            fwrite(&id1, 4, 1, f); fwrite(&len1, 8, 1, f); fwrite(&n8, 4, 1, f); fwrite(c->q.w, 32, 1, f); fwrite(&nw, 4, 1, f);
+            fwrite(&id1, 4, 1, f); fwrite(&len1, 8, 1, f); fwrite(&n8, 4, 1, f); fwrite(c->q.w, n8, 1, f); fwrite(&nw, 4, 1, f);
             fwrite(&id2, 4, 1, f); fwrite(&len2, 8, 1, f);
             fwrite(buf.data() + (size_t)k * row, 1, row, f);
             fclose(f);
@@ -3412,7 +3437,6 @@ static std::string u256_dec(const uint8_t le[32]) {
 }
 extern "C" int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, char *out, size_t out_len) {
     if (!b || !out || out_len == 0) return fail(CW_EINVAL, "null argument");
-    NOT_FOR_64(b, "cw_explain");
     if (instance >= b->batch) return fail(CW_EINVAL, "instance out of range");
     cw_circuit *c = b->c;
     std::vector<uint32_t> st(b->batch), fb(b->batch);
@@ -3449,6 +3473,27 @@ extern "C" int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, 
     if (s & CW_ST_R1CS_FAILED) {
         const uint32_t k = fb[instance];
         t += "constraint " + std::to_string(k) + " of the .r1cs is violated: A*B - C != 0 with\n";
+        if (c->is64) {
+            // the terms of constraint k: behind k row-end flags of the term list (a slot below n_signals IS the signal)
+            const std::vector<uint32_t> &tm = c->r1_terms64;
+            size_t q = 0;
+            for (uint32_t row = 0; row < k && q < tm.size(); q += 4)
+                if (tm[q + 1] & 4u) row++;
+            const size_t begin = q;
+            for (uint32_t part = 0; part < 3; part++) {
+                t += std::string("  ") + "ABC"[part] + ":";
+                for (q = begin; q < tm.size(); q += 4) {
+                    if ((tm[q + 1] & 3u) == part) {
+                        uint8_t v[32];
+                        rc = cw_get_signal(b, instance, tm[q], v);
+                        if (rc) return rc;
+                        t += " " + name_of(tm[q]) + " = " + u256_dec(v) + ";";
+                    }
+                    if (tm[q + 1] & 4u) break;
+                }
+                t += "\n";
+            }
+        }
         for (size_t j = 0; j < c->r_orig.size(); j++) {
             if ((c->r_orig[j] & 0x7FFFFFFFu) != k) continue;
             for (int part = 0; part < 3; part++) {

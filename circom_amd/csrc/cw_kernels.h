@@ -66,3 +66,6 @@ hipError_t cwk64_r1cs(hipStream_t s, const void *chunks, uint32_t n_chunks, cons
                       uint32_t *status, uint32_t *first_bad);
 hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
                         void *out);
+// bulk egress as a tiled transpose: [count][n_wit][elem_bytes], elem_bytes = 8 or 32 (32: `out` 16-byte aligned)
+hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                        void *out, uint32_t elem_bytes);

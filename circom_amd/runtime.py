@@ -98,6 +98,8 @@ _SIGS = {
     "cw_get_witness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "cw_get_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_get_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_get_witnesses_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_element_bytes": (C.c_uint32, [C.c_void_p]),
     "cw_get_public": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_public_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_signal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
@@ -168,6 +170,7 @@ class Circuit:
         buf = C.create_string_buffer(32)
         L.cw_prime(h, buf)
         self.q = int.from_bytes(buf.raw, "little")
+        self.element_bytes = L.cw_element_bytes(h)              # n8 of the .wtns files: 8 for the 64-bit runtime, 32 otherwise
 
     def set_witness_list(self, signals):
         """egress of every batch created from now on hands out these signals (the witness of a simplified system: `--O1`,
@@ -379,6 +382,11 @@ class Batch:
     def witnesses_device(self, first: int, count: int, d_ptr: int) -> None:
         """canonical values of `count` instances written to device memory at d_ptr ([count][n_witness][32])"""
         _chk(lib().cw_get_witnesses_device(self.h, first, count, C.c_void_p(d_ptr)))
+
+    def witnesses_device_n8(self, first: int, count: int, d_ptr: int) -> None:
+        """the same with the element of the .wtns files ([count][n_witness][circuit.element_bytes]): 8 bytes per value for
+        circuits of the 64-bit runtime, witnesses_device for every other"""
+        _chk(lib().cw_get_witnesses_device_n8(self.h, first, count, C.c_void_p(d_ptr)))
 
     def signal(self, instance: int, slot: int) -> int:
         buf = C.create_string_buffer(32)

@@ -86,6 +86,9 @@ uint32_t cw_n_public(const cw_circuit *c);     /* nPubOut + nPubIn of the r1cs h
 uint64_t cw_n_rows(const cw_circuit *c);             /* schedule length */
 uint64_t cw_n_mmul(const cw_circuit *c);             /* Montgomery multiplications per instance in the schedule */
 void cw_prime(const cw_circuit *c, uint8_t le32[32]); /* Fr_q (fr.hpp) */
+/* n8 of the circuit's .wtns files (writeBinWitness: the prime's byte length): 8 for circuits of the 64-bit runtime
+ * (--prime goldilocks, common64/main.cpp), 32 otherwise */
+uint32_t cw_element_bytes(const cw_circuit *c);
 /* getInputSignalSize(h) (calcwit.cpp:99-102): size of input `name`, or -1 */
 int64_t cw_input_size(const cw_circuit *c, const char *name, uint32_t *start_slot);
 
@@ -139,7 +142,8 @@ int cw_set_inputs_device(cw_batch *b, const void *d_le32);
  * ceil(batch / 64), bit i of masks[g][k] = main input k of instance 64 g + i.  The reference reads one JSON number per
  * bit (main.cpp:243-286); the 32-byte-per-value bulk form moves 256 bytes per input BIT of a SHA-256 circuit, this form
  * one bit.  cw_set_inputs_bits copies from host memory; the _device form keeps reading the caller's device buffer
- * (same lifetime rule as cw_set_inputs_device).  CW_ESTATE for batches on the 256-bit schedule. */
+ * (same lifetime rule as cw_set_inputs_device).  CW_ESTATE for batches on the 256-bit schedule and for circuits of the
+ * 64-bit runtime (--prime goldilocks) - the only entry points that runtime does not serve. */
 int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks);
 int cw_set_inputs_bits_device(cw_batch *b, const void *d_masks);
 /* read back input k (slot cw_input_start()+k) of one instance as staged by the two per-signal setters */
@@ -182,7 +186,13 @@ int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out);
  * the first egress after a cw_run of a bit-plane batch waits for the evaluation (it has to know which instances were
  * re-run by the 256-bit schedule; every egress serves those from there). */
 int cw_get_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out);
-/* chunked form: `chunk` instances at a time into d_buf0 / d_buf1 in turn ([chunk][n_witness][32] each); `consume` is called
+/* the same with the element of the circuit's .wtns files: [count][n_witness][cw_element_bytes], canonical little-endian.
+ * For the 64-bit runtime that is 8 bytes per value - what a Goldilocks prover reads; the 32-byte image is three quarters
+ * zeros.  Same state and range checks; for circuits whose element is 32 bytes it IS cw_get_witnesses_device.
+ * 64-bit runtime: both forms are one tiled transpose (cw64.hip cw64_egress_kernel; d_out of the 32-byte form should be
+ * 16-byte aligned, as hipMalloc returns it - another address is served by the slower per-entry gather). */
+int cw_get_witnesses_device_n8(cw_batch *b, uint32_t first, uint32_t count, void *d_out);
+/* chunked form: `chunk` instances at a time into d_buf0 / d_buf1 in turn ([chunk][n_witness][32] each, every engine); `consume` is called
  * after each chunk's transpose has been enqueued on the batch's stream (passed as `stream`, a hipStream_t): work enqueued
  * there sees the chunk complete and orders the library's next write to that buffer behind itself.  Non-zero return of
  * `consume` aborts with CW_ESTATE.  (writeBinWitness's loop over getWitness(i), main.cpp:326-332, for a consumer that
@@ -199,9 +209,10 @@ int cw_get_public_device(cw_batch *b, void *d_out);
 int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]);
 /* writeBinWitness (main.cpp:288-334) */
 int cw_write_wtns(cw_batch *b, uint32_t instance, const char *path);
-/* `count` .wtns files from one bulk device transpose; `pattern` = printf pattern with one %u (instance number) */
+/* `count` .wtns files from one bulk device transpose; `pattern` = printf pattern with one %u (instance number).  The files
+ * are the ones cw_write_wtns writes (n8 = cw_element_bytes: the 64-bit runtime's rows leave the device 8 bytes per value). */
 int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern);
-/* The whole batch as ONE compact container (<name>.wtnsb): field elements for 256-bit batches, the BIT TABLE (1 bit per
+/* The whole batch as ONE compact container (<name>.wtnsb): field elements (n8 = cw_element_bytes) for 256-bit and 64-bit batches, the BIT TABLE (1 bit per
  * distinct signal value and instance + the slot of every witness element + full values of the instances the 256-bit schedule
  * re-ran) for bit-plane batches.  Format: csrc/cw_host.cpp at cw_write_wtnsb; reader / expander circom_amd/wtnsb.py
  * (`expand(i)` = the bytes cw_write_wtns writes for instance i, main.cpp:288-334). */
