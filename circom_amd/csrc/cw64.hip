@@ -71,20 +71,25 @@ __global__ void __launch_bounds__(256) cw64_init_kernel(uint64_t *V, uint32_t Bp
         first_bad[i] = 0xFFFFFFFFu;
     }
 }
-// inputs arrive as the boundary's 32-byte little-endian values [batch][n_in][32]; a value that is not a canonical residue
-// (upper words set, or >= p) is reduced, as Fr_str2element does for what loadJson reads
+// inputs arrive as [batch][n_in][EB] little-endian values: EB = 32, the boundary's element, or EB = 8, the element of this
+// runtime; a value that is not a canonical residue (upper words set, or >= p) is reduced, as Fr_str2element does for what
+// loadJson reads.  Lane = instance, blockIdx.y = input: consecutive lanes read values n_in * EB bytes apart.  This is the
+// kernel for narrow circuits and for a 32-byte image at an address that is no multiple of 16 (cw64_ingest_tiled_kernel below).
+template <int EB>
 __global__ void __launch_bounds__(256) cw64_ingest_kernel(const uint64_t *__restrict__ in, uint64_t *V, uint32_t input_start, uint32_t n_in,
                                                           uint32_t batch, uint32_t Bp) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
     if (i >= batch) return;
-    const uint64_t *p = in + ((size_t)i * n_in + k) * 4;
+    const uint64_t *p = in + ((size_t)i * n_in + k) * (EB / 8);
     uint64_t r = p[0] >= GL_P ? p[0] - GL_P : p[0];
-    // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2, 2^192 = (2^32 - 1)^3 (mod p)
-    const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e), e3 = gl_mul(e2, e);
-    if (p[1] | p[2] | p[3]) {
-        r = gl_add(r, gl_mul(p[1] >= GL_P ? p[1] - GL_P : p[1], e));
-        r = gl_add(r, gl_mul(p[2] >= GL_P ? p[2] - GL_P : p[2], e2));
-        r = gl_add(r, gl_mul(p[3] >= GL_P ? p[3] - GL_P : p[3], e3));
+    if (EB == 32) {
+        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2, 2^192 = (2^32 - 1)^3 (mod p)
+        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e), e3 = gl_mul(e2, e);
+        if (p[1] | p[2] | p[3]) {
+            r = gl_add(r, gl_mul(p[1] >= GL_P ? p[1] - GL_P : p[1], e));
+            r = gl_add(r, gl_mul(p[2] >= GL_P ? p[2] - GL_P : p[2], e2));
+            r = gl_add(r, gl_mul(p[3] >= GL_P ? p[3] - GL_P : p[3], e3));
+        }
     }
     V[(size_t)(input_start + k) * Bp + i] = r;
 }
@@ -258,17 +263,143 @@ __global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__rest
     }
 }
 
+// Bulk ingest as the same transpose in the other direction: [batch][n_in][EB] bytes, EB = 32 (the boundary's element) or 8 (this
+// runtime's), into V[input_start + k][instance].  cw64_ingest_kernel gives consecutive lanes consecutive INSTANCES: every lane
+// reads another row of the image, n_in * EB bytes from its neighbour's - 64 cache lines for 512 useful bytes, and each of those
+// lines is asked for again by the workgroups of up to n_in other inputs.  Here a workgroup of four waves owns 64 instances x
+// EG_T inputs, and no other workgroup requests a byte of its part of the image:
+//   read    wave w takes the instances j = w, w + 4, ... of the tile; consecutive lanes read consecutive pieces of the row
+//           in[j0 + j][k0 .. k0 + EG_T): 8-byte form: the 64 values, 512 contiguous bytes (8-byte loads: with n_in odd a row
+//           starts on an 8-byte boundary only); 32-byte form: 16-byte pieces, lane l holds words {0, 1} (l even) or {2, 3} (l odd)
+//           of value l / 2 (+ 32 in the second load), 1 KiB contiguous per load, two loads per row.  `in` must be 16-byte
+//           aligned in the 32-byte form.  The 16 (32) loads of a wave are issued before the first value is used.
+//   reduce  8-byte form: one conditional subtraction of p.  32-byte form: w0 + w1 e + w2 e^2 + w3 e^3 with e = 2^32 - 1 = 2^64
+//           (mod p), every word brought below p first.  The even lane forms w0 + w1 e, the odd lane (w2 + w3 e) e^2, and one
+//           exchange between neighbours adds the two.  Nearly every real input has words 1..3 zero: a ballot over the wave
+//           (even lanes: w1, odd lanes: w2 | w3) skips multiplications and exchange for the whole load - the branch is
+//           wave-uniform, and a wave pays for the long form only for the loads that hold such a value.
+//   stage   tile[k][j] in LDS with rows of EG_S = 65 words of 8 bytes, the egress kernel's tile written and read the other way
+//           round.  Column-wise write (ds_write_b64: four groups of 16 consecutive lanes, bank = (a/4) % 32): lane l writes word
+//           l' * 65 + j with l' = l (8-byte form) or l / 2 (32-byte form, even lanes only), dwords 130 l' + 2 j and the next one,
+//           bank pair 2 ((l' + j) % 16): the 16 (or 8) rows l' of a group are consecutive and fall on distinct pairs, every
+//           bank at most once.  With rows of 64 words all lanes of a group would hit pair 2 (j % 16): 16-way.  Row-wise read
+//           (ds_read_b64: two groups of 32 lanes, bank = (a/4) % 64): a group reads 32 consecutive words = 64 consecutive dwords,
+//           every bank once, whatever the row's start.
+//           (This is arithmetic from the documented bank rules, as the egress comment is: nobody has taken a bank-conflict
+//           counter pass on either kernel.)
+//   write   wave w takes the inputs k = w, w + 4, ...; its 64 lanes store 64 consecutive instances of V[input_start + k0 + k]:
+//           one 512-byte store, as the evaluation kernel writes its results.
+// Lanes past `batch` and inputs past n_in neither read nor write; nothing is read past the end of the image.
+template <int EB>
+__global__ void __launch_bounds__(256) cw64_ingest_tiled_kernel(const uint8_t *__restrict__ in, uint64_t *__restrict__ V, uint32_t input_start,
+                                                                uint32_t n_in, uint32_t batch, uint32_t Bp) {
+    __shared__ uint64_t tile[EG_T * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
+    const uint32_t nk = n_in - k0 < EG_T ? n_in - k0 : EG_T, nj = batch - j0 < 64u ? batch - j0 : 64u;
+    // The loads of a wave stand in ONE block of straight-line code under the lane's own condition, the same for all of them (the
+    // row bases are wave-uniform: scalar registers, the lane is the offset).  A condition per load would make every load a branch
+    // of its own that waits for its data before the next one is issued.  The last instance tile of a batch (nj < 64) has a row
+    // condition too and takes that slower form.
+    if (EB == 8) {
+        const uint64_t *t0 = (const uint64_t *)in + (size_t)j0 * n_in + k0;
+        uint64_t v[64 / 4] = {};
+        if (lane < nk) {
+            if (nj == 64u) {
+#pragma unroll
+                for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * n_in + lane];
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 64 / 4; i++)
+                    if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * n_in + lane];
+            }
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 64 / 4; i++) tile[lane * EG_S + wave + 4 * i] = gl_wrap(v[i]);
+    } else {
+        const uint4 *t0 = (const uint4 *)in + ((size_t)j0 * n_in + k0) * 2;
+        const bool odd = lane & 1u;
+        uint4 v[64 / 4][2] = {};
+        if (nj == 64u && nk == EG_T) {                                 // a full tile: all 32 loads of the wave in one block
+#pragma unroll
+            for (uint32_t i = 0; i < 64 / 4; i++) {
+                v[i][0] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane];
+                v[i][1] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64];
+            }
+        } else
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {
+            if (((lane + 64 * h) >> 1) < nk) {
+                if (nj == 64u) {
+#pragma unroll
+                    for (uint32_t i = 0; i < 64 / 4; i++) v[i][h] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64 * h];
+                } else {
+#pragma unroll
+                    for (uint32_t i = 0; i < 64 / 4; i++)
+                        if (wave + 4 * i < nj) v[i][h] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64 * h];
+                }
+            }
+        }
+        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2 (mod p)
+        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e);
+#pragma unroll
+        for (uint32_t i = 0; i < 64 / 4; i++) {
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint64_t lo = ((uint64_t)v[i][h].y << 32) | v[i][h].x, hi = ((uint64_t)v[i][h].w << 32) | v[i][h].z;
+                uint64_t r = gl_wrap(lo);
+                if (__builtin_amdgcn_ballot_w64(odd ? (lo | hi) != 0 : hi != 0)) {
+                    uint64_t part = gl_add(r, gl_mul(gl_wrap(hi), e));
+                    if (odd) part = gl_mul(part, e2);
+                    r = gl_add(part, (uint64_t)__shfl_xor((unsigned long long)part, 1));
+                }
+                if (!odd) tile[((lane >> 1) + 32 * h) * EG_S + wave + 4 * i] = r;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = wave; k < nk; k += 4)
+        if (lane < nj) V[(size_t)(input_start + k0 + k) * Bp + j0 + lane] = tile[k * EG_S + lane];
+}
+
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 hipError_t cwk64_init(hipStream_t s, void *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad) {
     hipLaunchKernelGGL(cw64_init_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, (uint64_t *)V, Bp, status, first_bad);
     return hipGetLastError();
 }
-hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp) {
+// elem_bytes = 8 or 32; the input index is a grid dimension: at most 65 535 inputs (cwk64_ingest_tiled has no such limit)
+hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
+                        uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
     if (!n_in) return hipSuccess;
     if (n_in > 65535u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cw64_ingest_kernel, dim3((batch + 255) / 256, n_in), dim3(256), 0, s, (const uint64_t *)in, (uint64_t *)V, input_start,
-                       n_in, batch, Bp);
+    const dim3 grid((batch + 255) / 256, n_in);
+    if (elem_bytes == 8)
+        hipLaunchKernelGGL(cw64_ingest_kernel<8>, grid, dim3(256), 0, s, (const uint64_t *)in, (uint64_t *)V, input_start, n_in, batch, Bp);
+    else
+        hipLaunchKernelGGL(cw64_ingest_kernel<32>, grid, dim3(256), 0, s, (const uint64_t *)in, (uint64_t *)V, input_start, n_in, batch, Bp);
     return hipGetLastError();
+}
+// elem_bytes = 8 (`in` 8-byte aligned) or 32 (16-byte aligned); a launch holds at most 65 535 tiles of 64 instances (gridDim.y),
+// larger batches are split as cwk64_egress splits them; the input tiles are gridDim.x, so n_in is not limited
+hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
+                              uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if ((uintptr_t)in & (elem_bytes == 32 ? 15 : 7)) return hipErrorInvalidValue;
+    if (!n_in || !batch) return hipSuccess;
+    const uint32_t per = 65535u * 64u;
+    for (uint32_t done = 0; done < batch; done += per) {
+        const uint32_t n = batch - done < per ? batch - done : per;
+        const dim3 grid((n_in + EG_T - 1) / EG_T, (n + 63) / 64);
+        const uint8_t *i = (const uint8_t *)in + (size_t)done * n_in * elem_bytes;
+        uint64_t *v = (uint64_t *)V + done;
+        if (elem_bytes == 8)
+            hipLaunchKernelGGL(cw64_ingest_tiled_kernel<8>, grid, dim3(256), 0, s, i, v, input_start, n_in, n, Bp);
+        else
+            hipLaunchKernelGGL(cw64_ingest_tiled_kernel<32>, grid, dim3(256), 0, s, i, v, input_start, n_in, n, Bp);
+        if (hipError_t e = hipGetLastError()) return e;              // nothing more is launched behind a launch that failed
+    }
+    return hipSuccess;
 }
 hipError_t cwk64_eval(hipStream_t s, const void *rows, uint32_t n_rows, const void *consts, void *V, uint32_t Bp, uint32_t batch,
                       uint32_t *status) {

@@ -1723,6 +1723,9 @@ struct cw_batch {
     DevBuf<uint64_t> d_V64, d_consts64;
     DevBuf<uint32_t> d_rows64, d_terms64, d_chunks64;
     bool egress_tiled = true;                          // CW64_EGRESS_TILED=0: the 32-byte bulk forms go through cw64_gather_kernel (A/B timing)
+    int ingest_tiled = -1;                             // CW64_INGEST_TILED: 0 = cw64_ingest_kernel, 1 = the tiled kernel, unset = by input count
+    uint32_t in_eb = 32;                               // element bytes of the current bulk inputs (d_in / ext_in): 8 after cw_set_inputs*_n8
+    uint32_t rc_eb = 32;                               // ... and of the inputs the captured launches of cw_run_check read
     DevBuf<uint64_t> d_r1flag;                         // per group: instances whose fused R1CS check fired (emitted code)
     // cw_batch_set_timing: events on the batch's stream around the parts of cw_run / cw_check_r1cs (their own intervals, measured
     // where they run - bench.py's roofline figures): 0 run begins | 1 inputs ingested | 2 evaluation done | 3 check begins | 4 check done
@@ -2238,6 +2241,7 @@ static int set_input_hashed(cw_batch *b, uint32_t inst, uint64_t h, uint32_t idx
     b->host_dirty = true;
     b->ext_in = nullptr;
     b->packed_in = nullptr;
+    b->in_eb = 32;
     return CW_OK;
 }
 
@@ -2275,6 +2279,7 @@ extern "C" int cw_set_inputs(cw_batch *b, const uint8_t *le32) {
         b->all_set = true;
         b->host_dirty = true;
         b->ext_in = nullptr;
+        b->in_eb = 32;
         return CW_OK;
     }
     HIPCHK(hipSetDevice(b->device));
@@ -2283,6 +2288,7 @@ extern "C" int cw_set_inputs(cw_batch *b, const uint8_t *le32) {
     HIPCHK(hipStreamSynchronize(b->stream));   // caller may free le32 on return
     b->packed_in = nullptr;
     b->ext_in = nullptr;
+    b->in_eb = 32;
     b->host_dirty = false;
     b->all_set = true;
     std::fill(b->remaining.begin(), b->remaining.end(), 0);
@@ -2323,6 +2329,50 @@ extern "C" int cw_set_inputs_device(cw_batch *b, const void *d_le32) {
     if (!b || !d_le32) return fail(CW_EINVAL, "null argument");
     b->packed_in = nullptr;
     b->ext_in = d_le32;
+    b->in_eb = 32;
+    b->host_dirty = false;
+    b->all_set = true;
+    std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    return CW_OK;
+}
+
+// The 8-byte bulk forms of the 64-bit runtime: [batch][n_inputs][cw_element_bytes].  For every other circuit the element is 32
+// bytes and these ARE cw_set_inputs / cw_set_inputs_device (as cw_get_witnesses_device_n8 is cw_get_witnesses_device).
+extern "C" int cw_set_inputs_n8(cw_batch *b, const void *le8) {
+    if (!b || !le8) return fail(CW_EINVAL, "null argument");
+    if (!b->c->is64) return cw_set_inputs(b, (const uint8_t *)le8);
+    const size_t cells = (size_t)b->batch * b->c->n_inputs;
+    if (b->device < 0) {                                     // host-only batch: staged zero-extended, unreduced, as cw_set_inputs stages
+        ensure_host_staging(b);
+        std::fill(b->h_in.begin(), b->h_in.end(), 0);
+        for (size_t i = 0; i < cells; i++) memcpy(&b->h_in[i * 32], (const uint8_t *)le8 + i * 8, 8);
+        std::fill(b->assigned.begin(), b->assigned.end(), 1);
+        std::fill(b->remaining.begin(), b->remaining.end(), 0);
+        b->all_set = true;
+        b->host_dirty = true;
+        b->ext_in = nullptr;
+        b->in_eb = 32;                                       // the staging image is the 32-byte form
+        return CW_OK;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = ensure_d_in(b)) return rc;                  // sized for the 32-byte form: the 8-byte image takes its first quarter
+    HIPCHK(hipMemcpyAsync(b->d_in, le8, cells * 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));                 // caller may free le8 on return
+    b->packed_in = nullptr;
+    b->ext_in = nullptr;
+    b->in_eb = 8;
+    b->host_dirty = false;
+    b->all_set = true;
+    std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    return CW_OK;
+}
+extern "C" int cw_set_inputs_device_n8(cw_batch *b, const void *d_le8) {
+    if (!b || !d_le8) return fail(CW_EINVAL, "null argument");
+    if (!b->c->is64) return cw_set_inputs_device(b, d_le8);
+    if ((uintptr_t)d_le8 & 7) return fail(CW_EINVAL, "cw_set_inputs_device_n8: the image of 8-byte elements must be 8-byte aligned");
+    b->packed_in = nullptr;
+    b->ext_in = d_le8;
+    b->in_eb = 8;
     b->host_dirty = false;
     b->all_set = true;
     std::fill(b->remaining.begin(), b->remaining.end(), 0);
@@ -2528,6 +2578,12 @@ extern "C" int cw_set_inputs_json(cw_batch *b, uint32_t instance, const char *js
 // bit-plane mode
 // ---------------------------------------------------------------------------------------------------------
 // 64-bit runtime (cw64.hip): value table [slot][Bp] of uint64, the flat program, the R1CS terms
+// Input count from which cw_run ingests through cw64_ingest_tiled_kernel unless CW64_INGEST_TILED says otherwise.
+// Measured, not guessed: tools/ubench_ingest64.py, profiles/ingest64_chain_65536.json, the table at the top of NOTES.md.  64 is the
+// smallest measured count (2, 16, 64, 1 024) at which the transpose is no slower than the kernel it replaces in BOTH element
+// widths; nothing was measured between 16 and 64.  ONE threshold for both widths on purpose: the 8-byte form already wins at 16
+// inputs (by less than a tenth), the 32-byte form does not, and a second constant for that is not worth its test.
+static const uint32_t CW64_INGEST_TILE_MIN = 64;
 static int batch_setup64(cw_batch *b) {
     cw_circuit *c = b->c;
     b->v_bytes = (size_t)c->n_slots64 * b->Bp * 8;
@@ -2545,6 +2601,7 @@ static int batch_setup64(cw_batch *b) {
     HIPCHK(b->d_in.alloc(std::max<size_t>((size_t)b->batch * c->n_inputs * 32, 32)));
     HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
     if (const char *e = getenv("CW64_EGRESS_TILED")) b->egress_tiled = atoi(e) != 0;
+    if (const char *e = getenv("CW64_INGEST_TILED")) b->ingest_tiled = atoi(e) != 0;
     HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
     HIPCHK(hipStreamSynchronize(b->stream));
     return CW_OK;
@@ -2756,7 +2813,15 @@ extern "C" int cw_run(cw_batch *b) {
     if (c->is64) {
         TMARK(b, 0);
         HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
-        HIPCHK(cwk64_ingest(b->stream, in, b->d_V64, c->input_start, c->n_inputs, b->batch, b->Bp));
+        // the tiled transpose from CW64_INGEST_TILE_MIN inputs upwards, and wherever the other kernel's grid cannot hold the
+        // inputs; its 16-byte loads need an aligned image, so a 32-byte image at an odd address takes the lane-per-instance kernel
+        // (beyond 65 535 inputs that kernel's grid cannot hold the circuit: CW64_INGEST_TILED=0 does not apply there)
+        bool tiled = c->n_inputs > 65535u || (b->ingest_tiled < 0 ? c->n_inputs >= CW64_INGEST_TILE_MIN : b->ingest_tiled != 0);
+        if (b->in_eb == 32 && ((uintptr_t)in & 15)) tiled = false;
+        if (tiled)
+            HIPCHK(cwk64_ingest_tiled(b->stream, in, b->d_V64, c->input_start, c->n_inputs, b->batch, b->Bp, b->in_eb));
+        else
+            HIPCHK(cwk64_ingest(b->stream, in, b->d_V64, c->input_start, c->n_inputs, b->batch, b->Bp, b->in_eb));
         TMARK(b, 1);
         HIPCHK(cwk64_eval(b->stream, b->d_rows64, (uint32_t)(c->rows64.size() / 8), b->d_consts64, b->d_V64, b->Bp, b->batch, b->d_status));
         TMARK(b, 2);
@@ -2956,15 +3021,16 @@ extern "C" int cw_run_check(cw_batch *b) {
         return rc == CW_OK ? cw_check_r1cs(b) : rc;
     };
     const void *in = b->ext_in ? b->ext_in : b->d_in;
-    if (b->rc_graph && (b->rc_in != in || b->rc_packed != b->packed_in || b->timing || b->host_dirty)) {
+    if (b->rc_graph && (b->rc_in != in || b->rc_eb != b->in_eb || b->rc_packed != b->packed_in || b->timing || b->host_dirty)) {
         hipGraphExecDestroy(b->rc_graph);
         b->rc_graph = nullptr;
         b->rc_calls = 0;
     }
     if (b->timing || b->host_dirty || b->rc_failed || getenv("CW_NO_GRAPH")) return plain();
     if (!b->rc_graph) {
-        if (b->rc_in != in || b->rc_packed != b->packed_in) {
+        if (b->rc_in != in || b->rc_eb != b->in_eb || b->rc_packed != b->packed_in) {
             b->rc_in = in;
+            b->rc_eb = b->in_eb;
             b->rc_packed = b->packed_in;
             b->rc_calls = 0;
         }

@@ -59,7 +59,12 @@ hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, co
 
 // ---- 64-bit runtime (cw64.hip: --prime goldilocks) ----
 hipError_t cwk64_init(hipStream_t s, void *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad);
-hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp);
+// inputs [batch][n_in][elem_bytes], elem_bytes = 8 or 32: lane = instance (n_in <= 65 535) / a tiled transpose (8: `in` 8-byte
+// aligned, 32: 16-byte aligned; any n_in)
+hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
+                        uint32_t elem_bytes);
+hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
+                              uint32_t elem_bytes);
 hipError_t cwk64_eval(hipStream_t s, const void *rows, uint32_t n_rows, const void *consts, void *V, uint32_t Bp, uint32_t batch,
                       uint32_t *status);
 hipError_t cwk64_r1cs(hipStream_t s, const void *chunks, uint32_t n_chunks, const void *terms, const void *V, uint32_t Bp, uint32_t batch,

@@ -77,6 +77,8 @@ _SIGS = {
     "cw_set_inputs_json": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "cw_set_inputs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cw_set_inputs_n8": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cw_set_inputs_device_n8": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_bits": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_bits_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_stream_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -281,6 +283,15 @@ class Batch:
         assert arr.size == self.n * self.circuit.n_inputs * 32, "input array has the wrong size"
         _chk(lib().cw_set_inputs(self.h, arr.ctypes.data_as(C.c_void_p)))
 
+    def set_inputs_n8(self, arr):
+        """the bulk form with the circuit's own element (cw_set_inputs_n8).  64-bit runtime: a uint64 array [batch, n_inputs] or a
+        list of lists of ints below 2^64 (values >= p are reduced on the device); any other circuit: what set_inputs takes."""
+        if self.circuit.element_bytes == 32:
+            return self.set_inputs(arr)
+        arr = np.ascontiguousarray(np.asarray(arr, dtype=np.uint64), dtype="<u8")
+        assert arr.size == self.n * self.circuit.n_inputs, "input array has the wrong size"
+        _chk(lib().cw_set_inputs_n8(self.h, arr.ctypes.data_as(C.c_void_p)))
+
     def set_inputs_bits(self, masks):
         """packed boolean inputs: uint64 [groups][n_inputs], bit i of masks[g][k] = input k of instance 64 g + i"""
         arr = np.ascontiguousarray(masks, dtype=np.uint64)
@@ -298,6 +309,10 @@ class Batch:
 
     def set_inputs_device(self, dptr: int):
         _chk(lib().cw_set_inputs_device(self.h, C.c_void_p(dptr)))
+
+    def set_inputs_device_n8(self, dptr: int):
+        """device image [batch][n_inputs][element_bytes], 8-byte aligned (cw_set_inputs_device_n8)"""
+        _chk(lib().cw_set_inputs_device_n8(self.h, C.c_void_p(dptr)))
 
     def staged_input(self, instance: int, k: int) -> int:
         buf = C.create_string_buffer(32)

@@ -138,6 +138,26 @@ int cw_set_inputs(cw_batch *b, const uint8_t *le32);
  * order) and, in bit-plane batches, once more by the first cw_sync / getter after it - instances whose inputs are not 0/1
  * are re-run by the 256-bit schedule from these bytes - so it must stay unmodified until then. */
 int cw_set_inputs_device(cw_batch *b, const void *d_le32);
+/* The same two with the circuit's own element: [batch][n_inputs][cw_element_bytes] little-endian values.  For the 64-bit
+ * runtime (--prime goldilocks) that is 8 bytes per value - what a Goldilocks prover holds; the 32-byte image is three
+ * quarters zeros.  For circuits whose element is 32 bytes these ARE cw_set_inputs / cw_set_inputs_device.
+ *   values     need not be canonical: a value >= p is reduced on the device (one subtraction), as Fr_str2element reduces what
+ *              loadJson reads; the 32-byte forms reduce all four words the same way.  On a host-only batch the host form stages
+ *              each value zero-extended to 32 bytes, unreduced (cw_get_staged_input).
+ *   alignment  d_le8 must be 8-byte aligned (CW_EINVAL otherwise; the pointer is not touched before cw_run).  A 32-byte device
+ *              image should be 16-byte aligned, as hipMalloc returns it: another address is served by the slower
+ *              lane-per-instance kernel.
+ *   lifetime   cw_set_inputs_n8 copies and synchronises before it returns; d_le8 is read by cw_run in stream order and
+ *              must stay unmodified until that run has finished (the rule of cw_set_inputs_device).
+ *   size       64-bit runtime: from CW64_INGEST_TILE_MIN inputs upwards (cw_host.cpp, a measured threshold), and always beyond
+ *              65 535 inputs, both element sizes enter through one tiled transpose (cw64.hip cw64_ingest_tiled_kernel), which
+ *              has no limit on the number of inputs.  Only a 32-byte image at an address that is no multiple of 16 is still
+ *              limited to 65 535 inputs (CW_EDEVICE from cw_run).
+ * Any other setter puts the batch back on the 32-byte form.  CW64_INGEST_TILED=0 / 1, read at cw_batch_create, forces the
+ * lane-per-instance / the tiled kernel (A/B timing, tools/ubench_ingest64.py); beyond 65 535 inputs =0 is ignored, the
+ * lane-per-instance kernel cannot hold such a circuit. */
+int cw_set_inputs_n8(cw_batch *b, const void *le8);
+int cw_set_inputs_device_n8(cw_batch *b, const void *d_le8);
 /* Bit-plane batches (cw_batch_bitmode) only: PACKED boolean inputs, uint64 masks[groups][n_inputs], groups =
  * ceil(batch / 64), bit i of masks[g][k] = main input k of instance 64 g + i.  The reference reads one JSON number per
  * bit (main.cpp:243-286); the 32-byte-per-value bulk form moves 256 bytes per input BIT of a SHA-256 circuit, this form
