@@ -20,6 +20,7 @@
 #include "cw_r1cs_plan.h"
 #include "cw_bits_host.h"
 #include "cw_devbuf.h"
+#include "cw_rerun.h"
 
 typedef unsigned __int128 u128;
 
@@ -1650,6 +1651,14 @@ extern "C" int cw_r1cs_stream_plan(const cw_circuit *c, uint32_t terms_per_chunk
 // ---------------------------------------------------------------------------------------------------------
 static const uint64_t PIPE_MAX_GROUPS = 4096;
 
+// what the launches of cw_run read their inputs from: the image (caller's or d_in), the packed masks, the element bytes.
+// cw_run_check keys its captured graph on it (a captured launch carries the pointers and the element size it was given).
+struct InputKey {
+    const void *in = nullptr, *packed = nullptr;
+    uint32_t eb = 32;
+    bool operator==(const InputKey &o) const { return in == o.in && packed == o.packed && eb == o.eb; }
+};
+
 struct cw_batch {
     cw_circuit *c = nullptr;
     int device = 0;
@@ -1673,10 +1682,11 @@ struct cw_batch {
     DevBuf<void> d_pmask;          // cw_set_inputs_bits: the caller's packed masks on the device (8 bytes per input and group)
     DevBuf<void> d_gather;         // [n_witness][32]
     DevBuf<void> d_bulk;           // staging of cw_get_witnesses: [rows][n_witness][32], grown to the largest piece asked for
+    // the source of the next run's bulk inputs: ext_in, packed_in and in_eb are written by set_input_source alone
     const void *ext_in = nullptr;  // caller-owned device inputs (cw_set_inputs_device)
     // cw_run_check: cw_run + cw_check_r1cs captured once as a HIP graph and replayed (one launch per step instead of ~10)
     hipGraphExec_t rc_graph = nullptr;
-    const void *rc_in = nullptr, *rc_packed = nullptr;   // the input pointers the captured launches carry
+    InputKey rc_key;                                      // the inputs the captured launches read
     uint32_t rc_calls = 0;                                // plain calls since the inputs last changed (the first loads modules)
     bool rc_failed = false;                               // a capture of these launches failed once: cw_run_check stays on the plain calls
     // argument blocks of the emitted kernels (hipModuleLaunchKernel's `extra` form): members, not locals - a captured launch
@@ -1725,7 +1735,6 @@ struct cw_batch {
     bool egress_tiled = true;                          // CW64_EGRESS_TILED=0: the 32-byte bulk forms go through cw64_gather_kernel (A/B timing)
     int ingest_tiled = -1;                             // CW64_INGEST_TILED: 0 = cw64_ingest_kernel, 1 = the tiled kernel, unset = by input count
     uint32_t in_eb = 32;                               // element bytes of the current bulk inputs (d_in / ext_in): 8 after cw_set_inputs*_n8
-    uint32_t rc_eb = 32;                               // ... and of the inputs the captured launches of cw_run_check read
     DevBuf<uint64_t> d_r1flag;                         // per group: instances whose fused R1CS check fired (emitted code)
     // cw_batch_set_timing: events on the batch's stream around the parts of cw_run / cw_check_r1cs (their own intervals, measured
     // where they run - bench.py's roofline figures): 0 run begins | 1 inputs ingested | 2 evaluation done | 3 check begins | 4 check done
@@ -2213,6 +2222,24 @@ extern "C" uint32_t cw_batch_pipelined(const cw_batch *b) { return b && b->var &
 extern "C" uint32_t cw_batch_emitted(const cw_batch *b) { return b && b->fp_fn ? (b->fp_covered ? 2 : 1) : 0; }
 extern "C" uint32_t cw_batch_lanes(const cw_batch *b) { return b->bitmode ? b->bits_width : b->lanes; }
 
+// ---- where the next run's inputs come from ----
+// The one writer of ext_in / packed_in / in_eb (and the one that sets host_dirty; cw_run clears it).  `ext`: a caller-owned device image, or nullptr for the batch's own
+// d_in (which cw_run fills from the host staging h_in first while `dirty`); `packed`: packed masks instead of an image; eb: the
+// image's element bytes.  A bulk call is `complete`: nothing is left to assign.  Per-signal assignment (set_input_hashed) is
+// not, and keeps its own count in `remaining`.
+static void set_input_source(cw_batch *b, const void *ext, const void *packed, uint32_t eb, bool dirty, bool complete = true) {
+    b->ext_in = ext;
+    b->packed_in = packed;
+    b->in_eb = eb;
+    b->host_dirty = dirty;
+    if (complete) {
+        b->all_set = true;
+        std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    }
+}
+static const void *input_image(const cw_batch *b) { return b->ext_in ? b->ext_in : b->d_in.get(); }
+static InputKey input_key(const cw_batch *b) { return InputKey{input_image(b), b->packed_in, b->in_eb}; }
+
 static int ensure_host_staging(cw_batch *b) {
     size_t n = (size_t)b->batch * b->c->n_inputs;
     if (b->h_in.size() != n * 32) b->h_in.assign(n * 32, 0);
@@ -2238,10 +2265,7 @@ static int set_input_hashed(cw_batch *b, uint32_t inst, uint64_t h, uint32_t idx
     memcpy(&b->h_in[cell * 32], val, 32);
     b->assigned[cell] = 1;
     b->remaining[inst]--;
-    b->host_dirty = true;
-    b->ext_in = nullptr;
-    b->packed_in = nullptr;
-    b->in_eb = 32;
+    set_input_source(b, nullptr, nullptr, 32, true, false);
     return CW_OK;
 }
 
@@ -2268,43 +2292,50 @@ extern "C" int64_t cw_remaining_inputs(const cw_batch *b, uint32_t instance) {
     return b->remaining[instance];
 }
 
-extern "C" int cw_set_inputs(cw_batch *b, const uint8_t *le32) {
-    if (!b || !le32) return fail(CW_EINVAL, "null argument");
-    size_t n = (size_t)b->batch * b->c->n_inputs * 32;
-    if (b->device < 0) {                                     // host-only batch: stage (every cell counts as assigned)
+// The bulk setters.  Host image [batch][n_inputs][eb]: a host-only batch stages it zero-extended to the 32-byte form, unreduced
+// (every cell counts as assigned); a device batch copies it into d_in as it is (sized for the 32-byte form: an 8-byte image
+// takes its first quarter).  eb = 8 is the 64-bit runtime's own element (cw_set_inputs_n8); for every other circuit the element
+// is 32 bytes and the _n8 calls ARE cw_set_inputs / cw_set_inputs_device (as cw_get_witnesses_device_n8 is
+// cw_get_witnesses_device).
+static int set_inputs_host(cw_batch *b, const void *img, uint32_t eb) {
+    if (!b || !img) return fail(CW_EINVAL, "null argument");
+    const size_t cells = (size_t)b->batch * b->c->n_inputs;
+    if (b->device < 0) {
         ensure_host_staging(b);
-        memcpy(b->h_in.data(), le32, n);
+        if (eb == 32)
+            memcpy(b->h_in.data(), img, cells * 32);
+        else {
+            std::fill(b->h_in.begin(), b->h_in.end(), 0);
+            for (size_t i = 0; i < cells; i++) memcpy(&b->h_in[i * 32], (const uint8_t *)img + i * eb, eb);
+        }
         std::fill(b->assigned.begin(), b->assigned.end(), 1);
-        std::fill(b->remaining.begin(), b->remaining.end(), 0);
-        b->all_set = true;
-        b->host_dirty = true;
-        b->ext_in = nullptr;
-        b->in_eb = 32;
+        set_input_source(b, nullptr, nullptr, 32, true);         // the staging image is the 32-byte form
         return CW_OK;
     }
     HIPCHK(hipSetDevice(b->device));
     if (int rc = ensure_d_in(b)) return rc;
-    HIPCHK(hipMemcpyAsync(b->d_in, le32, n, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));   // caller may free le32 on return
-    b->packed_in = nullptr;
-    b->ext_in = nullptr;
-    b->in_eb = 32;
-    b->host_dirty = false;
-    b->all_set = true;
-    std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    HIPCHK(hipMemcpyAsync(b->d_in, img, cells * eb, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));                     // caller may free the image on return
+    set_input_source(b, nullptr, nullptr, eb, false);
     return CW_OK;
 }
+static int set_inputs_device(cw_batch *b, const void *d_img, uint32_t eb) {
+    if (!b || !d_img) return fail(CW_EINVAL, "null argument");
+    if (eb == 8 && ((uintptr_t)d_img & 7)) return fail(CW_EINVAL, "cw_set_inputs_device_n8: the image of 8-byte elements must be 8-byte aligned");
+    set_input_source(b, d_img, nullptr, eb, false);
+    return CW_OK;
+}
+extern "C" int cw_set_inputs(cw_batch *b, const uint8_t *le32) { return set_inputs_host(b, le32, 32); }
+extern "C" int cw_set_inputs_n8(cw_batch *b, const void *le8) { return set_inputs_host(b, le8, b ? cw_element_bytes(b->c) : 32); }
+extern "C" int cw_set_inputs_device(cw_batch *b, const void *d_le32) { return set_inputs_device(b, d_le32, 32); }
+extern "C" int cw_set_inputs_device_n8(cw_batch *b, const void *d_le8) { return set_inputs_device(b, d_le8, b ? cw_element_bytes(b->c) : 32); }
 
 extern "C" int cw_set_inputs_bits_device(cw_batch *b, const void *d_masks) {
     if (!b || !d_masks) return fail(CW_EINVAL, "null argument");
     NOT_FOR_64(b, "packed boolean inputs");
     NEED_DEVICE(b);
     if (!b->bitmode) return fail(CW_ESTATE, "packed boolean inputs need a bit-plane batch (cw_batch_bitmode)");
-    b->packed_in = d_masks;
-    b->ext_in = nullptr;
-    b->host_dirty = false;
-    b->all_set = true;
-    std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    set_input_source(b, nullptr, d_masks, 32, false);
     return CW_OK;
 }
 extern "C" int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks) {
@@ -2323,60 +2354,6 @@ extern "C" int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks) {
     HIPCHK(hipMemcpyAsync(b->d_pmask, masks, nbytes, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return cw_set_inputs_bits_device(b, b->d_pmask);
-}
-
-extern "C" int cw_set_inputs_device(cw_batch *b, const void *d_le32) {
-    if (!b || !d_le32) return fail(CW_EINVAL, "null argument");
-    b->packed_in = nullptr;
-    b->ext_in = d_le32;
-    b->in_eb = 32;
-    b->host_dirty = false;
-    b->all_set = true;
-    std::fill(b->remaining.begin(), b->remaining.end(), 0);
-    return CW_OK;
-}
-
-// The 8-byte bulk forms of the 64-bit runtime: [batch][n_inputs][cw_element_bytes].  For every other circuit the element is 32
-// bytes and these ARE cw_set_inputs / cw_set_inputs_device (as cw_get_witnesses_device_n8 is cw_get_witnesses_device).
-extern "C" int cw_set_inputs_n8(cw_batch *b, const void *le8) {
-    if (!b || !le8) return fail(CW_EINVAL, "null argument");
-    if (!b->c->is64) return cw_set_inputs(b, (const uint8_t *)le8);
-    const size_t cells = (size_t)b->batch * b->c->n_inputs;
-    if (b->device < 0) {                                     // host-only batch: staged zero-extended, unreduced, as cw_set_inputs stages
-        ensure_host_staging(b);
-        std::fill(b->h_in.begin(), b->h_in.end(), 0);
-        for (size_t i = 0; i < cells; i++) memcpy(&b->h_in[i * 32], (const uint8_t *)le8 + i * 8, 8);
-        std::fill(b->assigned.begin(), b->assigned.end(), 1);
-        std::fill(b->remaining.begin(), b->remaining.end(), 0);
-        b->all_set = true;
-        b->host_dirty = true;
-        b->ext_in = nullptr;
-        b->in_eb = 32;                                       // the staging image is the 32-byte form
-        return CW_OK;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    if (int rc = ensure_d_in(b)) return rc;                  // sized for the 32-byte form: the 8-byte image takes its first quarter
-    HIPCHK(hipMemcpyAsync(b->d_in, le8, cells * 8, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));                 // caller may free le8 on return
-    b->packed_in = nullptr;
-    b->ext_in = nullptr;
-    b->in_eb = 8;
-    b->host_dirty = false;
-    b->all_set = true;
-    std::fill(b->remaining.begin(), b->remaining.end(), 0);
-    return CW_OK;
-}
-extern "C" int cw_set_inputs_device_n8(cw_batch *b, const void *d_le8) {
-    if (!b || !d_le8) return fail(CW_EINVAL, "null argument");
-    if (!b->c->is64) return cw_set_inputs_device(b, d_le8);
-    if ((uintptr_t)d_le8 & 7) return fail(CW_EINVAL, "cw_set_inputs_device_n8: the image of 8-byte elements must be 8-byte aligned");
-    b->packed_in = nullptr;
-    b->ext_in = d_le8;
-    b->in_eb = 8;
-    b->host_dirty = false;
-    b->all_set = true;
-    std::fill(b->remaining.begin(), b->remaining.end(), 0);
-    return CW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2606,17 +2583,6 @@ static int batch_setup64(cw_batch *b) {
     HIPCHK(hipStreamSynchronize(b->stream));
     return CW_OK;
 }
-// bulk egress of the 64-bit runtime: [count][n_witness][eb] at d_out, eb = 32 or 8, asynchronous on the batch's stream.  The tiled
-// transpose serves both; its 16-byte stores need an aligned destination, so a 32-byte image at an odd address takes the gather.
-static int egress64(cw_batch *b, uint32_t first, uint32_t count, void *d_out, uint32_t eb) {
-    const cw_circuit *c = b->c;
-    if (eb == 32 && (!b->egress_tiled || ((uintptr_t)d_out & 15)))
-        HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, first, count, d_out));
-    else
-        HIPCHK(cwk64_egress(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, first, count, d_out, eb));
-    return CW_OK;
-}
-
 static int bits_batch_setup(cw_batch *b) {
     cw_circuit *c = b->c;
     const cwbits::Program &bp = c->bits;
@@ -2775,13 +2741,10 @@ static int bits_resolve(cw_batch *b) {
         HIPCHK(hipMemcpyAsync(b->d_fbinst, inst.data(), inst.size() * 4, hipMemcpyHostToDevice, b->stream));
         // one kernel gathers the inputs of the listed instances (from the packed masks or the 32-byte image the caller
         // handed over: that buffer must stay unmodified until the first cw_sync / getter after cw_run, see circom_amd.h)
-        HIPCHK(cwk_bits_collect_inputs(b->stream, b->packed_in, b->packed_in ? nullptr : (b->ext_in ? b->ext_in : b->d_in), b->d_fbinst,
+        HIPCHK(cwk_bits_collect_inputs(b->stream, b->packed_in, b->packed_in ? nullptr : input_image(b), b->d_fbinst,
                                      (uint32_t)inst.size(), c->n_inputs, b->fb->d_in));
         HIPCHK(hipStreamSynchronize(b->stream));                       // `inst` goes out of scope
-        b->fb->ext_in = nullptr;
-        b->fb->host_dirty = false;
-        b->fb->all_set = true;
-        std::fill(b->fb->remaining.begin(), b->fb->remaining.end(), 0);
+        set_input_source(b->fb, nullptr, nullptr, 32, false);
         int rc = cw_run(b->fb);
         if (rc == CW_OK && b->checked && c->n_constraints) rc = cw_check_r1cs(b->fb);
         if (rc != CW_OK) return rc;
@@ -2809,7 +2772,7 @@ extern "C" int cw_run(cw_batch *b) {
         HIPCHK(hipMemcpyAsync(b->d_in, b->h_in.data(), b->h_in.size(), hipMemcpyHostToDevice, b->stream));
         b->host_dirty = false;
     }
-    const void *in = b->ext_in ? b->ext_in : b->d_in;
+    const void *in = input_image(b);
     if (c->is64) {
         TMARK(b, 0);
         HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
@@ -3020,18 +2983,17 @@ extern "C" int cw_run_check(cw_batch *b) {
         int rc = cw_run(b);
         return rc == CW_OK ? cw_check_r1cs(b) : rc;
     };
-    const void *in = b->ext_in ? b->ext_in : b->d_in;
-    if (b->rc_graph && (b->rc_in != in || b->rc_eb != b->in_eb || b->rc_packed != b->packed_in || b->timing || b->host_dirty)) {
+    const InputKey key = input_key(b);
+    const bool same = key == b->rc_key;
+    if (b->rc_graph && (!same || b->timing || b->host_dirty)) {
         hipGraphExecDestroy(b->rc_graph);
         b->rc_graph = nullptr;
         b->rc_calls = 0;
     }
     if (b->timing || b->host_dirty || b->rc_failed || getenv("CW_NO_GRAPH")) return plain();
     if (!b->rc_graph) {
-        if (b->rc_in != in || b->rc_eb != b->in_eb || b->rc_packed != b->packed_in) {
-            b->rc_in = in;
-            b->rc_eb = b->in_eb;
-            b->rc_packed = b->packed_in;
+        if (!same) {
+            b->rc_key = key;
             b->rc_calls = 0;
         }
         if (b->rc_calls++ == 0) return plain();           // loads the code objects, makes every lazy allocation
@@ -3117,13 +3079,26 @@ extern "C" int cw_get_r1cs_first_bad(cw_batch *b, uint32_t *row) {
     return bits_patch_words(b, row, true);
 }
 
-extern "C" int cw_get_witness(cw_batch *b, uint32_t instance, uint8_t *out) {
-    if (!b || !out) return fail(CW_EINVAL, "null argument");
-    if (instance >= b->batch) return fail(CW_EINVAL, "instance out of range");
+// What every getter of results checks first, in this order; `who` names the call in the text of the state error.
+static int getter_ready(cw_batch *b, const void *arg, const char *who, uint32_t first = 0, uint32_t count = 0,
+                        const char *range_msg = "instance range out of the batch") {
+    if (!b || !arg) return fail(CW_EINVAL, "null argument");
+    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, range_msg);
     NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_get_witness before cw_run");
-    cw_circuit *c = b->c;
+    if (!b->ran) return fail(CW_ESTATE, std::string(who) + " before cw_run");
     HIPCHK(hipSetDevice(b->device));
+    return CW_OK;
+}
+// rows of `row` bytes in one piece of a bulk transfer: 256 MiB worth, not more than `count`, at least one
+static uint32_t piece_rows(size_t row, uint32_t count) {
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
+}
+
+// One instance.  Apart from device_egress below for its kernels: the 256-bit engine has a single-instance gather, and an
+// instance of the side batch is fetched from there whole.
+extern "C" int cw_get_witness(cw_batch *b, uint32_t instance, uint8_t *out) {
+    if (int rc = getter_ready(b, out, "cw_get_witness", instance, 1, "instance out of range")) return rc;
+    cw_circuit *c = b->c;
     if (c->is64) {
         HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s, c->n_witness, b->Bp, instance, 1, b->d_gather));
     } else if (b->bitmode) {
@@ -3131,101 +3106,79 @@ extern "C" int cw_get_witness(cw_batch *b, uint32_t instance, uint8_t *out) {
         if (b->fb_index[instance] >= 0) return cw_get_witness(b->fb, (uint32_t)b->fb_index[instance], out);
         HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot, c->n_witness, instance, 1, b->d_gather));
     } else
-    HIPCHK(cwk_gather(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, instance, b->d_gather, c->mont, c->P));
+        HIPCHK(cwk_gather(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, instance, b->d_gather, c->mont, c->P));
     HIPCHK(hipMemcpyAsync(out, b->d_gather, (size_t)c->n_witness * 32, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return CW_OK;
 }
 
-// Bulk form: `count` instances starting at `first`, [count][n_witness][32 B], transposed on the device and
-// copied in pieces of at most 256 MiB through a staging buffer that is allocated on first use.
+// The bulk egress of every engine: entries [skip, skip + n) of the witness list, for the instances [first, first + count), as
+// canonical little-endian elements of eb bytes, [count][n][eb] in DEVICE memory at d_out; asynchronous on the batch's stream.
+// The witness calls pass skip = 0, n = n_witness; the public signals skip = 1, n = n_public and tiled_ok = false.
+//  - 64-bit runtime: the tiled transpose serves both element sizes; its 16-byte stores need an aligned destination, so a 32-byte
+//    image at an odd address takes the gather, as does every 32-byte image under CW64_EGRESS_TILED=0 and every call that does
+//    not allow the transpose (the gather writes 32-byte elements only).
+//  - bit-plane: this is where a bit becomes a field element again.  The instances the bit program could not serve (inputs that
+//    are not 0/1, assertion gates) are known only after the evaluation: the first egress of a run waits for it (one stream
+//    synchronisation + an 8-byte-per-group copy), then everything is asynchronous.  Their rows come from the side batch, one
+//    gather per run of consecutive instances, written over the rows the bit table gave.  When the whole batch went through the
+//    256-bit schedule (more than a quarter of it was not boolean: fb_inst is the identity) the side batch serves the range in
+//    ONE gather and the bit table is not consulted.
+static int device_egress(cw_batch *b, uint32_t skip, uint32_t n, uint32_t first, uint32_t count, void *d_out, uint32_t eb, bool tiled_ok) {
+    const cw_circuit *c = b->c;
+    if (c->is64) {
+        if (!tiled_ok || (eb == 32 && (!b->egress_tiled || ((uintptr_t)d_out & 15))))
+            HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s + skip, n, b->Bp, first, count, d_out));
+        else
+            HIPCHK(cwk64_egress(b->stream, b->d_V64, b->d_w2s + skip, n, b->Bp, first, count, d_out, eb));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return device_egress(b->fb, skip, n, first, count, d_out, eb, tiled_ok);
+        HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + skip, n, first, count, d_out));
+        const size_t row = (size_t)n * eb;
+        return cw_rerun_runs(b->fb_inst, first, count, [&](uint32_t pos, uint32_t len, uint32_t off) {
+            return device_egress(b->fb, skip, n, pos, len, (char *)d_out + (size_t)off * row, eb, tiled_ok);
+        });
+    }
+    HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s + skip, n, b->Bp, first, count, d_out, c->mont, c->P));
+    return CW_OK;
+}
+
+// Bulk form: `count` instances starting at `first`, [count][n_witness][eb], transposed on the device and copied in pieces
+// (multiples of 64 instances, at least 64) through a staging buffer that is allocated on first use.
 // eb = bytes per element in `out`: 32, or cw_element_bytes(c) (8 for the 64-bit runtime: the bodies of its .wtns files).
 static int get_witnesses_host(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out, uint32_t eb) {
-    if (!b || !out) return fail(CW_EINVAL, "null argument");
-    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
-    NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_get_witnesses before cw_run");
-    cw_circuit *c = b->c;
-    HIPCHK(hipSetDevice(b->device));
-    if (int rc = bits_resolve(b)) return rc;
+    if (int rc = getter_ready(b, out, "cw_get_witnesses", first, count)) return rc;
+    const cw_circuit *c = b->c;
     const size_t row = (size_t)c->n_witness * eb;
-    uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
-    per = std::max<uint32_t>(64, per / 64 * 64);
+    const uint32_t per = std::max<uint32_t>(64, piece_rows(row, count) / 64 * 64);
     HIPCHK(b->d_bulk.grow((size_t)per * row));
     for (uint32_t done = 0; done < count; done += per) {
         const uint32_t n = std::min(per, count - done);
-        if (c->is64) {
-            if (int rc = egress64(b, first + done, n, b->d_bulk, eb)) return rc;
-        } else if (b->bitmode)
-            HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot, c->n_witness, first + done, n, b->d_bulk));
-        else
-            HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, first + done, n, b->d_bulk, c->mont, c->P));
+        if (int rc = device_egress(b, 0, c->n_witness, first + done, n, b->d_bulk, eb, true)) return rc;
         HIPCHK(hipMemcpyAsync(out + (size_t)done * row, b->d_bulk, (size_t)n * row, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
     }
-    if (b->bitmode)
-        for (size_t k = 0; k < b->fb_inst.size();) {              // runs of consecutive re-run instances: one bulk call each
-            size_t e = k + 1;
-            while (e < b->fb_inst.size() && b->fb_inst[e] == b->fb_inst[e - 1] + 1) e++;
-            const uint32_t lo = std::max(b->fb_inst[k], first), hi = (uint32_t)std::min<uint64_t>((uint64_t)b->fb_inst[e - 1] + 1, (uint64_t)first + count);
-            if (lo < hi)
-                if (int rc = cw_get_witnesses(b->fb, (uint32_t)(k + (lo - b->fb_inst[k])), hi - lo, out + (size_t)(lo - first) * row)) return rc;
-            k = e;
-        }
     return CW_OK;
 }
 extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) { return get_witnesses_host(b, first, count, out, 32); }
 extern "C" uint32_t cw_element_bytes(const cw_circuit *c) { return c && c->is64 ? 8 : 32; }
 
 // Device-side form for GPU provers: canonical 32-byte values of `count` instances written to DEVICE memory
-// ([count][n_witness][32]); no host copy.  In bit-plane batches this is where a bit becomes a field element again.
+// ([count][n_witness][32]); no host copy.
 extern "C" int cw_get_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
-    if (!b || !d_out) return fail(CW_EINVAL, "null argument");
-    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
-    NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_get_witnesses_device before cw_run");
-    cw_circuit *c = b->c;
-    HIPCHK(hipSetDevice(b->device));
-    if (c->is64) return egress64(b, first, count, d_out, 32);
-    if (!b->bitmode) {
-        HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s, c->n_witness, b->Bp, first, count, d_out, c->mont, c->P));
-        return CW_OK;
-    }
-    // instances the bit-plane program could not serve (inputs that are not 0/1, assertion gates) are known only after
-    // the evaluation: the first egress of a run waits for it (one stream synchronisation + an 8-byte-per-group copy),
-    // then everything below is asynchronous on the batch's stream
-    if (int rc = bits_resolve(b)) return rc;
-    // the whole batch went through the 256-bit schedule (more than a quarter of it was not boolean: fb_inst is the identity):
-    // the side batch serves the range in ONE gather; the bit table is not consulted
-    if (b->resolved && b->fb && b->fb_inst.size() == b->batch) return cw_get_witnesses_device(b->fb, first, count, d_out);
-    HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot, c->n_witness, first, count, d_out));
-    if (b->resolved) {
-        // re-run instances: consecutive positions of the side batch that are consecutive instances leave in one gather
-        const size_t row = (size_t)c->n_witness * 32;
-        for (size_t k = 0; k < b->fb_inst.size();) {
-            size_t e = k + 1;
-            while (e < b->fb_inst.size() && b->fb_inst[e] == b->fb_inst[e - 1] + 1) e++;
-            const uint32_t lo = std::max(b->fb_inst[k], first), hi = std::min<uint64_t>((uint64_t)b->fb_inst[e - 1] + 1, (uint64_t)first + count);
-            if (lo < hi) {
-                int rc = cw_get_witnesses_device(b->fb, (uint32_t)(k + (lo - b->fb_inst[k])), hi - lo, (char *)d_out + (size_t)(lo - first) * row);
-                if (rc != CW_OK) return rc;
-            }
-            k = e;
-        }
-    }
-    return CW_OK;
+    if (int rc = getter_ready(b, d_out, "cw_get_witnesses_device", first, count)) return rc;
+    return device_egress(b, 0, b->c->n_witness, first, count, d_out, 32, true);
 }
 
 // The same with the element the circuit's .wtns files carry (cw_element_bytes): [count][n_witness][8] for the 64-bit runtime -
 // all a Goldilocks prover reads; three quarters of the 32-byte image are zeros.  Every other circuit: the call above.
 extern "C" int cw_get_witnesses_device_n8(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
-    if (!b || !d_out) return fail(CW_EINVAL, "null argument");
-    if (!b->c->is64) return cw_get_witnesses_device(b, first, count, d_out);
-    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
-    NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_get_witnesses_device_n8 before cw_run");
-    HIPCHK(hipSetDevice(b->device));
-    return egress64(b, first, count, d_out, 8);
+    if (b && !b->c->is64) return cw_get_witnesses_device(b, first, count, d_out);
+    if (int rc = getter_ready(b, d_out, "cw_get_witnesses_device_n8", first, count)) return rc;
+    return device_egress(b, 0, b->c->n_witness, first, count, d_out, 8, true);
 }
 
 // Chunked device-side egress for provers: the canonical image of `count` instances does not fit anywhere for a
@@ -3253,37 +3206,11 @@ extern "C" int cw_stream_witnesses_device(cw_batch *b, uint32_t first, uint32_t 
 // Public signals of every instance, [batch][n_public][32], written to DEVICE memory: what a multi-GPU job gathers to
 // the root next to the status words and what a verifier needs (snarkjs public.json).
 extern "C" int cw_get_public_device(cw_batch *b, void *d_out) {
-    if (!b || !d_out) return fail(CW_EINVAL, "null argument");
-    NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_get_public_device before cw_run");
-    cw_circuit *c = b->c;
-    const uint32_t np = cw_n_public(c);
+    if (int rc = getter_ready(b, d_out, "cw_get_public_device")) return rc;
+    const uint32_t np = cw_n_public(b->c);
     if (np == 0) return CW_OK;
-    if (np >= c->n_witness) return fail(CW_ESTATE, "public signal count exceeds the witness");
-    HIPCHK(hipSetDevice(b->device));
-    if (b->bitmode) {
-        if (int rc = bits_resolve(b)) return rc;
-        HIPCHK(cwk_bits_gather(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + 1, np, 0, b->batch, d_out));
-        if (!b->fb_inst.empty()) {
-            DevBuf<void> tmp;
-            const size_t prow = (size_t)np * 32;
-            HIPCHK(tmp.alloc((size_t)b->fb->batch * prow));
-            int rc = cw_get_public_device(b->fb, tmp);
-            for (size_t k = 0; rc == CW_OK && k < b->fb_inst.size(); k++)
-                if (hipMemcpyAsync((char *)d_out + (size_t)b->fb_inst[k] * prow, (char *)tmp.get() + k * prow, prow, hipMemcpyDeviceToDevice,
-                                   b->stream) != hipSuccess)
-                    rc = fail(CW_EDEVICE, "copy of re-run public signals failed");
-            hipStreamSynchronize(b->stream);   // the copies read `tmp`
-            return rc;
-        }
-        return CW_OK;
-    }
-    if (c->is64) {
-        HIPCHK(cwk64_gather(b->stream, b->d_V64, b->d_w2s + 1, np, b->Bp, 0, b->batch, d_out));
-        return CW_OK;
-    }
-    HIPCHK(cwk_gather_many(b->stream, b->d_V, b->d_w2s + 1, np, b->Bp, 0, b->batch, d_out, c->mont, c->P));
-    return CW_OK;
+    if (np >= b->c->n_witness) return fail(CW_ESTATE, "public signal count exceeds the witness");
+    return device_egress(b, 1, np, 0, b->batch, d_out, 32, false);
 }
 extern "C" int cw_get_public(cw_batch *b, uint8_t *out) {
     if (!b || !out) return fail(CW_EINVAL, "null argument");
@@ -3339,34 +3266,31 @@ extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint
     return CW_OK;
 }
 
-// writeBinWitness (main.cpp:288-334)
+// writeBinWitness (main.cpp:288-334): the header, then the body of n_witness elements of n8 bytes.  n8 = the prime's byte
+// length: 32 for the 4-limb primes, 8 for the 64-bit runtime (common64/main.cpp writeBinWitness).
+static int write_wtns_file(const cw_circuit *c, const char *path, const uint8_t *body) {
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
+    const uint32_t version = 2, nsec = 2, id1 = 1, n8 = cw_element_bytes(c), id2 = 2, nw = c->n_witness;
+    const uint64_t len1 = 8 + n8, len2 = (uint64_t)n8 * nw;
+    bool ok = fwrite("wtns", 4, 1, f) == 1;
+    ok &= fwrite(&version, 4, 1, f) == 1 && fwrite(&nsec, 4, 1, f) == 1;
+    ok &= fwrite(&id1, 4, 1, f) == 1 && fwrite(&len1, 8, 1, f) == 1;
+    ok &= fwrite(&n8, 4, 1, f) == 1 && fwrite(c->q.w, n8, 1, f) == 1 && fwrite(&nw, 4, 1, f) == 1;
+    ok &= fwrite(&id2, 4, 1, f) == 1 && fwrite(&len2, 8, 1, f) == 1;
+    ok &= fwrite(body, 1, len2, f) == len2;
+    ok &= fclose(f) == 0;
+    return ok ? CW_OK : fail(CW_EIO, std::string("short write: ") + path);
+}
 extern "C" int cw_write_wtns(cw_batch *b, uint32_t instance, const char *path) {
     if (!b || !path) return fail(CW_EINVAL, "null argument");
     cw_circuit *c = b->c;
     std::vector<uint8_t> w((size_t)c->n_witness * 32);
     int rc = cw_get_witness(b, instance, w.data());
     if (rc) return rc;
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
-    // n8 = the prime's byte length: 32 for the 4-limb primes, 8 for the 64-bit runtime (common64/main.cpp writeBinWitness)
-    uint32_t version = 2, nsec = 2, id1 = 1, n8 = c->is64 ? 8 : 32, id2 = 2, nw = c->n_witness;
-    uint64_t len1 = 8 + n8, len2 = (uint64_t)n8 * nw;
-    fwrite("wtns", 4, 1, f);
-    fwrite(&version, 4, 1, f);
-    fwrite(&nsec, 4, 1, f);
-    fwrite(&id1, 4, 1, f);
-    fwrite(&len1, 8, 1, f);
-    fwrite(&n8, 4, 1, f);
-    fwrite(c->q.w, n8, 1, f);
-    fwrite(&nw, 4, 1, f);
-    fwrite(&id2, 4, 1, f);
-    fwrite(&len2, 8, 1, f);
-    if (c->is64)
-        for (uint32_t k = 0; k < nw; k++) fwrite(&w[(size_t)k * 32], 8, 1, f);
-    else
-        fwrite(w.data(), 1, w.size(), f);
-    fclose(f);
-    return CW_OK;
+    if (c->is64)                                                     // 32-byte elements in, 8-byte elements in the file
+        for (uint32_t k = 1; k < c->n_witness; k++) memmove(&w[(size_t)k * 8], &w[(size_t)k * 32], 8);
+    return write_wtns_file(c, path, w.data());
 }
 
 // The whole batch as ONE compact container (`<name>.wtnsb`, format below; reader + expander: circom_amd/wtnsb.py).  The
@@ -3382,11 +3306,8 @@ extern "C" int cw_write_wtns(cw_batch *b, uint32_t instance, const char *path) {
 //            u32 n_wide | n_wide x { u32 instance | n_witness x n8 bytes }: instances re-run by the 256-bit schedule (inputs
 //            that are not 0/1, tripped assertions) carry their field elements
 extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
-    if (!b || !path) return fail(CW_EINVAL, "null argument");
-    NEED_DEVICE(b);
-    if (!b->ran) return fail(CW_ESTATE, "cw_write_wtnsb before cw_run");
+    if (int rc = getter_ready(b, path, "cw_write_wtnsb")) return rc;
     cw_circuit *c = b->c;
-    HIPCHK(hipSetDevice(b->device));
     if (int rc = bits_resolve(b)) return rc;
     FILE *f = fopen(path, "wb");
     if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
@@ -3397,7 +3318,7 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
     const size_t row = (size_t)nw * n8;
     int rc = CW_OK;
     if (!b->bitmode) {
-        const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(batch, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
+        const uint32_t per = piece_rows(row, batch);
         std::vector<uint8_t> buf((size_t)per * row);
         for (uint32_t done = 0; done < batch && rc == CW_OK && ok; done += per) {
             const uint32_t n = std::min(per, batch - done);
@@ -3455,7 +3376,7 @@ extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, c
     cw_circuit *c = b->c;
     const uint32_t eb = cw_element_bytes(c);        // 8 for the 64-bit runtime: its rows leave the device as the files hold them
     const size_t row = (size_t)c->n_witness * eb;
-    const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>(count, ((size_t)256 << 20) / std::max<size_t>(row, 1)));
+    const uint32_t per = piece_rows(row, count);
     std::vector<uint8_t> buf((size_t)per * row);
     for (uint32_t done = 0; done < count; done += per) {
         const uint32_t n = std::min(per, count - done);
@@ -3464,15 +3385,7 @@ extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, c
         for (uint32_t k = 0; k < n; k++) {
             char path[4096];
             snprintf(path, sizeof path, pattern, first + done + k);
-            FILE *f = fopen(path, "wb");
-            if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
-            uint32_t version = 2, nsec = 2, id1 = 1, n8 = eb, id2 = 2, nw = c->n_witness;
-            uint64_t len1 = 8 + n8, len2 = (uint64_t)n8 * nw;
-            fwrite("wtns", 4, 1, f); fwrite(&version, 4, 1, f); fwrite(&nsec, 4, 1, f);
-            fwrite(&id1, 4, 1, f); fwrite(&len1, 8, 1, f); fwrite(&n8, 4, 1, f); fwrite(c->q.w, n8, 1, f); fwrite(&nw, 4, 1, f);
-            fwrite(&id2, 4, 1, f); fwrite(&len2, 8, 1, f);
-            fwrite(buf.data() + (size_t)k * row, 1, row, f);
-            fclose(f);
+            if (int rc = write_wtns_file(c, path, buf.data() + (size_t)k * row)) return rc;
         }
     }
     return CW_OK;

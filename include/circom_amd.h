@@ -227,7 +227,8 @@ int cw_get_public(cw_batch *b, uint8_t *out);
 int cw_get_public_device(cw_batch *b, void *d_out);
 /* one signal of one instance (signalValues[slot]) */
 int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]);
-/* writeBinWitness (main.cpp:288-334) */
+/* writeBinWitness (main.cpp:288-334).  Every write is checked, here and in the two calls below: a file that could not be
+ * written in full (a full disk) is CW_EIO "short write: <path>". */
 int cw_write_wtns(cw_batch *b, uint32_t instance, const char *path);
 /* `count` .wtns files from one bulk device transpose; `pattern` = printf pattern with one %u (instance number).  The files
  * are the ones cw_write_wtns writes (n8 = cw_element_bytes: the 64-bit runtime's rows leave the device 8 bytes per value). */

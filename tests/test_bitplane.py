@@ -850,6 +850,56 @@ def test_gpu_packed_inputs_and_chunked_egress(tmp_path, engine):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n_odd", [4, 40])
+def test_gpu_device_egress_patches_the_rerun_instances(tmp_path, engine, n_odd):
+    """cw_get_witnesses_device / cw_get_public_device of a batch with re-run instances: the bit table is gathered and the
+    instances of the side batch are patched in on the device, run by run, clipped to the window.  Instances 3, 64, 65, 129
+    give the runs {3}, {64, 65}, {129}; the windows cut before, between, inside and behind them.  With 40 such instances
+    (more than a quarter of 130) the side batch is the whole batch and serves every window alone."""
+    cp, c = _gpu(tmp_path, Program(BitGadget(8)), "bg8d")
+    hip = _Hip()
+    fc = cp.flat
+    B = 130
+    rows = _rand_bits(fc, B, 9)
+    odd = {3: (0, 2), 64: (5, c.q - 1), 65: (23, 12345678901234567890), 129: (7, 1 << 200)}
+    for i in range(70, 70 + n_odd - 4):
+        odd[i] = (i % 24, 2 + i)
+    assert len(odd) == n_odd
+    for i, (k, v) in odd.items():
+        rows[i][k] = v
+    b = c.batch(B)
+    assert b.bitmode and b.jit == (engine == "jit")
+    b.set_inputs(rows)
+    b.run(); b.check_r1cs(); b.sync()
+    st = b.status()
+    bulk = b.witnesses()
+    for i in range(B):                                         # the host image itself against the oracle
+        sig, failed = _flat(fc, rows[i])
+        assert (failed is not None) == bool(st[i] & 1), i
+        if failed is None:
+            assert [int.from_bytes(bulk[i, k].tobytes(), "little") for k in range(fc.n_signals)] == sig, i
+    row = c.n_witness * 32
+    for first, count in ((0, 130), (4, 60), (64, 1), (65, 65)):
+        p = hip.upload(np.full(count * row + 64, 0xA5, dtype=np.uint8))
+        b.witnesses_device(first, count, p)
+        b.sync()
+        got = hip.download(p, (count * row + 64,))
+        hip.h.hipFree(p)
+        assert (got[:count * row].reshape(count, c.n_witness, 32) == bulk[first:first + count]).all(), (first, count)
+        assert (got[count * row:] == 0xA5).all(), (first, count)
+    prow = c.n_public * 32
+    assert prow > 0
+    p = hip.upload(np.full(B * prow + 64, 0xA5, dtype=np.uint8))
+    b.public_signals_device(p)
+    b.sync()
+    got = hip.download(p, (B * prow + 64,))
+    hip.h.hipFree(p)
+    assert (got[:B * prow].reshape(B, c.n_public, 32) == bulk[:, 1:1 + c.n_public]).all()
+    assert (got[B * prow:] == 0xA5).all()
+    b.close(); c.close()
+
+
+@pytest.mark.gpu
 def test_gpu_compact_container_round_trips_to_the_wtns_files(tmp_path, engine):
     """cw_write_wtnsb: one file for the batch (bit planes + slot map + the field elements of the instances the 256-bit schedule
     re-ran); circom_amd/wtnsb.py expands it to exactly the bytes cw_write_wtns writes, for boolean and non-boolean instances"""

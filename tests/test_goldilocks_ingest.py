@@ -29,7 +29,7 @@ from oracle.tape_eval import eval_flat                                          
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_wtns_goldilocks.json")))["cases"]
 CASES = goldilocks_cases()
 Q = 18446744069414584321
-CW_EINVAL, CW_EDEVICE, CW_ESTATE = -2, -4, -5
+CW_EINVAL, CW_EINPUT, CW_EDEVICE, CW_ESTATE = -2, -3, -4, -5
 EDGE_K = (0, 63, 64, 128, 129)
 EDGES8 = (0, 1, Q - 1, Q, Q + 5, 2**64 - 1)
 TILED = pytest.mark.parametrize("tiled", ["1", "0"])
@@ -163,6 +163,46 @@ def test_host_only_staging_of_the_8_byte_form(tmp_path):
     with pytest.raises(rt.CwError) as e:
         b.run()
     assert e.value.code == CW_EDEVICE
+    b.close(); c.close()
+
+
+def _staged_after_every_bulk_setter(b, n, steps):
+    """each step = (setter, rows): afterwards nothing is left to assign, every cell reads back as the value just given
+    (zero-extended), and a per-signal assignment is refused as it is after the last input of the reference's setInputSignal"""
+    from circom_amd import runtime as rt
+    for setter, rows in steps:
+        setter(rows)
+        for i, row in enumerate(rows):
+            assert b.remaining_inputs(i) == 0
+            assert [b.staged_input(i, k) for k in range(n)] == list(row), i
+        with pytest.raises(rt.CwError) as e:
+            b.set_input_signal(0, "x", 0, 1)
+        assert e.value.code == CW_EINPUT and "No more signals to be assigned" in str(e.value)
+
+
+def test_host_only_bulk_setters_in_sequence(tmp_path):
+    """set_inputs_n8, set_inputs, set_inputs_n8 on one host-only batch of the chain circuit: the state after each call is that
+    call's alone, whichever form came before.  The 32-byte half again on a 256-bit circuit."""
+    from circom_amd import runtime as rt
+    n, B = 5, 3
+    r = random.Random(55)
+    cp = compile_program(Program(Chain(n), prime="goldilocks"), str(tmp_path), "chain5g", sym=False)
+    c = rt.Circuit(cp.tape_path, cp.dat_path, cp.r1cs_path)
+    assert c.element_bytes == 8 and c.n_inputs == n
+    b = c.batch(B, device=-1)
+    assert b.remaining_inputs(0) == n
+    rows8a = [[r.getrandbits(64) for _ in range(n)] for _ in range(B)]
+    rows32 = [[r.getrandbits(256) for _ in range(n)] for _ in range(B)]           # unreduced: staged as given
+    rows8b = [list(EDGES8[:n])] + [[r.getrandbits(64) for _ in range(n)] for _ in range(B - 1)]
+    _staged_after_every_bulk_setter(b, n, [(b.set_inputs_n8, rows8a), (b.set_inputs, rows32), (b.set_inputs_n8, rows8b)])
+    b.close(); c.close()
+    cp = compile_program(Program(Chain(n)), str(tmp_path), "chain5", sym=False)
+    c = rt.Circuit(cp.tape_path, cp.dat_path, cp.r1cs_path)
+    assert c.element_bytes == 32
+    b = c.batch(B, device=-1)
+    rows_a = [[r.randrange(c.q) for _ in range(n)] for _ in range(B)]
+    rows_b = [[c.q - 1, 0, 1, 1 << 200, 7]] + [[r.randrange(c.q) for _ in range(n)] for _ in range(B - 1)]
+    _staged_after_every_bulk_setter(b, n, [(b.set_inputs_n8, rows_a), (b.set_inputs, rows_b), (b.set_inputs_n8, rows_a)])
     b.close(); c.close()
 
 

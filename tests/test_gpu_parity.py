@@ -17,6 +17,7 @@ from oracle.field import Field, PRIMES, FieldError
 from oracle.tape_eval import eval_flat, check_r1cs
 
 pytestmark = pytest.mark.gpu
+CW_EIO = -1
 
 
 def _edges(f):
@@ -490,6 +491,27 @@ def test_bulk_wtns_files_and_failure_trace(tmp_path):
         if sgn > 0:
             assert " = %d;" % w[sgn] in text
     assert "instance 5" in b.explain(5)                 # without a .sym: signal numbers
+    b.close(); c.close()
+
+
+def test_wtns_writers_report_a_short_write(tmp_path):
+    """a device without space (/dev/full: every write fails with ENOSPC) behind the file name: both .wtns writers return
+    CW_EIO instead of leaving a truncated file and CW_OK"""
+    if not os.path.exists("/dev/full"):
+        pytest.skip("no /dev/full on this system")
+    from circom_amd.compiler import compile_program
+    cp = compile_program(Program(Multiplier2()), str(tmp_path), "m2full", sym=False)
+    c = rt.Circuit(cp.tape_path, cp.dat_path, cp.r1cs_path)
+    b = c.batch(1)
+    b.set_inputs([[3, 11]])
+    b.run(); b.sync()
+    os.symlink("/dev/full", tmp_path / "w0.wtns")
+    with pytest.raises(rt.CwError) as e:
+        b.write_wtns(0, tmp_path / "w0.wtns")
+    assert e.value.code == CW_EIO and "short write: " in str(e.value)
+    with pytest.raises(rt.CwError) as e:
+        b.write_wtns_many(0, 1, str(tmp_path / "w%u.wtns"))
+    assert e.value.code == CW_EIO and "short write: " in str(e.value)
     b.close(); c.close()
 
 
