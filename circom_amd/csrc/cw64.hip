@@ -6,7 +6,7 @@
 // "q is large" (short products without reduction, lazy integer sums, single-limb masks): none of that holds for a 64-bit
 // prime, and none of its machinery is needed - a value is ONE register.  So this file is its own small engine:
 //
-//   value table   V[slot][instance] : uint64, canonical residues, slot 0 = the constant 1, signals, then temporaries
+//   value table   V[slot][instance] : uint64, canonical residues, slot 0 = the constant 1, signals, hidden log values, temporaries
 //                 (one coalesced 512-byte access per wave and operand)
 //   program       the flat witness code, one 32-byte row per operation (hip_elements/lower64.py), wave-uniform
 //   one lane = one instance; operators follow the reference's 64-bit library exactly as oracle/field.py restates it for
@@ -95,15 +95,150 @@ __global__ void __launch_bounds__(256) cw64_ingest_kernel(const uint64_t *__rest
 }
 
 // row = 8 x u32: w0 = op | dk << 8 | ak << 10 | bk << 12 | ck << 14 (kind 0 = table slot, 2 = constant, 3 = none); dst; a; b; c;
-// index of the flat operation (failure reports); 0; 0
+// index of the flat operation (failure reports); 0; 0.  O_CALL: a = function id, b = slot of register 0 of the call's window.
 enum : uint32_t { O_COPY = 0, O_ADD, O_SUB, O_MUL, O_DIV, O_IDIV, O_MOD, O_POW, O_NEG, O_SHL, O_SHR, O_BAND, O_BOR, O_BXOR, O_BNOT,
-                  O_LT, O_GT, O_LEQ, O_GEQ, O_EQ, O_NEQ, O_LAND, O_LOR, O_LNOT, O_SELECT, O_ASSERT_EQ, O_ASSERT_NZ };
+                  O_LT, O_GT, O_LEQ, O_GEQ, O_EQ, O_NEQ, O_LAND, O_LOR, O_LNOT, O_SELECT, O_ASSERT_EQ, O_ASSERT_NZ, O_CALL };
+// the operators of the witness language on two values (O_COPY .. O_LNOT): what a row computes and what an instruction of a
+// function body computes.  An integer division or modulo by zero sets *fail and yields 0.
+__device__ __forceinline__ uint64_t gl_alu(uint32_t op, uint64_t a, uint64_t b, bool *fail) {
+    uint64_t d = 0;
+    switch (op) {
+    case O_COPY: d = a; break;
+    case O_ADD: d = gl_add(a, b); break;
+    case O_SUB: d = gl_sub(a, b); break;
+    case O_MUL: d = gl_mul(a, b); break;
+    case O_DIV: d = gl_mul(a, gl_inv(b)); break;
+    case O_IDIV: if (b == 0) *fail = true; else d = a / b; break;
+    case O_MOD: if (b == 0) *fail = true; else d = a % b; break;
+    case O_POW: d = gl_pow(a, b); break;
+    case O_NEG: d = gl_neg(a); break;
+    case O_SHL: d = gl_shl(a, b); break;
+    case O_SHR: d = gl_shr(a, b); break;
+    case O_BAND: d = gl_wrap(a & b); break;
+    case O_BOR: d = gl_wrap(a | b); break;
+    case O_BXOR: d = gl_wrap(a ^ b); break;
+    case O_BNOT: d = gl_wrap(~a); break;
+    case O_LT: d = gl_lt(a, b); break;
+    case O_GT: d = gl_lt(b, a); break;
+    case O_LEQ: d = !gl_lt(b, a); break;
+    case O_GEQ: d = !gl_lt(a, b); break;
+    case O_EQ: d = a == b; break;
+    case O_NEQ: d = a != b; break;
+    case O_LAND: d = (a != 0) & (b != 0); break;
+    case O_LOR: d = (a != 0) | (b != 0); break;
+    case O_LNOT: d = a == 0; break;
+    default: break;
+    }
+    return d;
+}
+
+// ---- O_CALL: a circom function with run-time control flow, interpreted per lane ----------------------------------------------
+// Reference: the emitted C++ of a function is real control flow on Fr_isTrue / Fr_toInt (loop_bucket.rs:76-91,
+// branch_bucket.rs:100-122, compute_bucket.rs:361-363, call_bucket.rs:466-533); trip counts differ per input, so the trace cannot
+// unroll it.  Structure of cw_call.hip.h eval_call_body, the 256-bit engine's interpreter: every lane has its own program counter;
+// per turn the wave executes the instruction of its unfinished lane with the LOWEST counter for all lanes that sit on it, the
+// others wait (rtcode.py's bytecode is structured - an `if` jumps forward over its body, a loop jumps back to its head - so lanes
+// that took different sides of a branch meet again at its join).  Bytecode: 4 x u32 {opcode, dst, a, b}, opcode = O_COPY ..
+// O_LNOT or F_* of cw_tape.h, operand = register or FN_CONST | constant index; cw_fn64.h checked every number when the tape
+// was loaded, so nothing here can leave the window, the constant table or the function's code.
+//
+// A lane fails and carries on, as oracle/tape_eval.py run_function does: an array index >= the array's length reads / writes
+// element 0, an integer division or modulo by zero yields 0; after CW_CALL_STEP_LIMIT instructions the lane is flagged and stops.
+//
+// The register window = n_regs consecutive temporaries of the lane's column, two placements behind fn_get / fn_set:
+//   table   register r = V[base + r][instance], as the 256-bit engine has it: every access is a 512-byte access of the wave, a
+//           run-time index makes it one row per lane
+//   LDS     win[r * 64 + lane] in 8-byte words (dynamic LDS, max_regs * 512 bytes for the workgroup's one wave): the window is
+//           copied in from the table when the call begins (one coalesced 512-byte load per register) and copied back when the
+//           last lane has returned, so the table stays the only state between rows and both placements leave the same bytes in
+//           it.  Banks: a row is 64 words = 128 dwords, a multiple of the 64-dword bank cycle of ds_read_b64 / ds_write_b64, so
+//           lane l sits on dword bank 2 l mod 64 WHATEVER register it addresses: the 32 lanes of a half-wave fall on 32 distinct
+//           bank pairs, for the wave-uniform register of an ordinary instruction and for the per-lane register of a run-time
+//           index alike - no conflicts.  (Arithmetic from the documented bank rules, as the egress and ingest comments below are;
+//           nobody has taken a bank-conflict counter pass on this kernel.)
+// A lane only ever touches its own column of either placement: no barrier, and lanes past the batch (already returned) are
+// never waited for - ballots count the lanes in EXEC only.
+extern __shared__ uint64_t cw64_win[];
+template <bool LDS>
+__device__ __forceinline__ uint64_t fn_get(const uint64_t *W, uint32_t Bp, uint32_t r) {
+    return LDS ? cw64_win[r * 64u + threadIdx.x] : W[(size_t)r * Bp];
+}
+template <bool LDS>
+__device__ __forceinline__ void fn_set(uint64_t *W, uint32_t Bp, uint32_t r, uint64_t v) {
+    if (LDS) cw64_win[r * 64u + threadIdx.x] = v;
+    else W[(size_t)r * Bp] = v;
+}
+template <bool LDS>
+__device__ __forceinline__ uint64_t fn_operand(uint32_t x, const uint64_t *W, uint32_t Bp, const uint64_t *__restrict__ consts) {
+    return x & FN_CONST ? consts[x & 0x7FFFFFFFu] : fn_get<LDS>(W, Bp, x);
+}
+// W = the lane's register 0 (V + base * Bp + instance); returns whether the lane failed
+template <bool LDS>
+__device__ __forceinline__ bool cw64_call(const uint4 *__restrict__ ftab, const uint4 *__restrict__ fcode, uint32_t fn, uint64_t *W, uint32_t Bp,
+                                          const uint64_t *__restrict__ consts) {
+    const uint4 ft = ftab[fn];                                          // {first instruction, n instructions, n registers, -}
+    const uint4 *code = fcode + ft.x;
+    const uint32_t lane = threadIdx.x;
+    if (LDS)
+        for (uint32_t r = 0; r < ft.z; r++) cw64_win[r * 64u + lane] = W[(size_t)r * Bp];
+    uint32_t pc = 0, steps = 0;
+    bool done = false, bad = false;
+    const int pc_bits = 32 - __builtin_clz(ft.y | 1u);                  // instruction indices are < ft.y (wave-uniform)
+    while (__builtin_amdgcn_ballot_w64(!done)) {
+        // the lowest program counter among the unfinished lanes, bit by bit with ballots
+        uint64_t cand = __builtin_amdgcn_ballot_w64(!done);
+        uint32_t cur = 0;
+        for (int bit = pc_bits - 1; bit >= 0; bit--) {
+            const uint64_t z = __builtin_amdgcn_ballot_w64(!done && ((cand >> lane) & 1ull) && !((pc >> bit) & 1u));
+            if (z) cand = z;
+            else cur |= 1u << bit;
+        }
+        if (!done && pc == cur) {
+            const uint4 ins = code[cur];                                // wave-uniform
+            const uint32_t op = ins.x, d = ins.y;
+            pc = cur + 1;
+            if (++steps > CW_CALL_STEP_LIMIT) {
+                bad = true;
+                done = true;
+            } else if (op == F_RET) {
+                done = true;
+            } else if (op == F_JMP) {
+                pc = d;
+            } else if (op == F_JZ) {
+                if (fn_operand<LDS>(ins.z, W, Bp, consts) == 0) pc = d;
+            } else if (op == F_LDX || op == F_STX) {
+                // Fr_toInt restricted to what an array address can be: [0, length) or "bad" (a "negative" value is >= 2^63)
+                const uint64_t iv = fn_get<LDS>(W, Bp, ins.w & 0xFFFFu);
+                uint32_t idx = (uint32_t)iv;
+                if (iv >= (uint64_t)(ins.w >> 16)) {
+                    bad = true;
+                    idx = 0;
+                }
+                if (op == F_LDX) fn_set<LDS>(W, Bp, d, fn_get<LDS>(W, Bp, ins.z + idx));
+                else fn_set<LDS>(W, Bp, d + idx, fn_operand<LDS>(ins.z, W, Bp, consts));
+            } else {
+                const uint64_t a = fn_operand<LDS>(ins.z, W, Bp, consts);
+                uint64_t b = 0;
+                if (op != O_COPY && op != O_NEG && op != O_BNOT && op != O_LNOT) b = fn_operand<LDS>(ins.w, W, Bp, consts);
+                fn_set<LDS>(W, Bp, d, gl_alu(op, a, b, &bad));
+            }
+        }
+    }
+    if (LDS)
+        for (uint32_t r = 0; r < ft.z; r++) W[(size_t)r * Bp] = cw64_win[r * 64u + lane];
+    return bad;
+}
+
 // (Round 6 tried requesting the operands of row r + 1 before row r computes, with register forwarding of a value the next row
 // reads: 1.15 ms instead of 0.96 ms for Poseidon(2) x 65 536 - the loads of one row already overlap across the waves of a SIMD,
 // the extra bookkeeping does not pay; profiles/r06i_bench_poseidon2_goldilocks.json has that run.  The check below is what
 // moved the line: 38 -> 59 M witnesses/s.)
+// CALLS: 0 = the program has no O_CALL row (no LDS, and the row loop has no branch for one), 1 = register windows in the table,
+// 2 = in LDS.  ftab / fcode are read by the other two only.
+template <int CALLS>
 __global__ void __launch_bounds__(64) cw64_eval_kernel(const uint4 *__restrict__ rows, uint32_t n_rows, const uint64_t *__restrict__ consts,
-                                                       uint64_t *V, uint32_t Bp, uint32_t batch, uint32_t *status) {
+                                                       uint64_t *V, uint32_t Bp, uint32_t batch, uint32_t *status,
+                                                       const uint4 *__restrict__ ftab, const uint4 *__restrict__ fcode) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= batch) return;
     uint64_t *Vi = V + i;
@@ -111,35 +246,15 @@ __global__ void __launch_bounds__(64) cw64_eval_kernel(const uint4 *__restrict__
     for (uint32_t r = 0; r < n_rows; r++) {
         const uint4 x = rows[2 * r], y = rows[2 * r + 1];               // wave-uniform: scalar loads
         const uint32_t op = x.x & 0xFF, ak = (x.x >> 10) & 3, bk = (x.x >> 12) & 3, ck = (x.x >> 14) & 3;
+        if (CALLS && op == O_CALL) {
+            if (cw64_call<CALLS == 2>(ftab, fcode, x.z, Vi + (size_t)x.w * Bp, Bp, consts) && !(st & 3u)) st = CW_ST_ARITH | (y.y << 8);
+            continue;
+        }
         const uint64_t a = ak == 0 ? Vi[(size_t)x.z * Bp] : ak == 2 ? consts[x.z] : 0;
         const uint64_t b = bk == 0 ? Vi[(size_t)x.w * Bp] : bk == 2 ? consts[x.w] : 0;
         uint64_t d = 0;
         bool fail = false;
         switch (op) {
-        case O_COPY: d = a; break;
-        case O_ADD: d = gl_add(a, b); break;
-        case O_SUB: d = gl_sub(a, b); break;
-        case O_MUL: d = gl_mul(a, b); break;
-        case O_DIV: d = gl_mul(a, gl_inv(b)); break;
-        case O_IDIV: if (b == 0) fail = true; else d = a / b; break;
-        case O_MOD: if (b == 0) fail = true; else d = a % b; break;
-        case O_POW: d = gl_pow(a, b); break;
-        case O_NEG: d = gl_neg(a); break;
-        case O_SHL: d = gl_shl(a, b); break;
-        case O_SHR: d = gl_shr(a, b); break;
-        case O_BAND: d = gl_wrap(a & b); break;
-        case O_BOR: d = gl_wrap(a | b); break;
-        case O_BXOR: d = gl_wrap(a ^ b); break;
-        case O_BNOT: d = gl_wrap(~a); break;
-        case O_LT: d = gl_lt(a, b); break;
-        case O_GT: d = gl_lt(b, a); break;
-        case O_LEQ: d = !gl_lt(b, a); break;
-        case O_GEQ: d = !gl_lt(a, b); break;
-        case O_EQ: d = a == b; break;
-        case O_NEQ: d = a != b; break;
-        case O_LAND: d = (a != 0) & (b != 0); break;
-        case O_LOR: d = (a != 0) | (b != 0); break;
-        case O_LNOT: d = a == 0; break;
         case O_SELECT: {
             const uint64_t cc = ck == 0 ? Vi[(size_t)y.x * Bp] : ck == 2 ? consts[y.x] : 0;
             d = a != 0 ? b : cc;
@@ -147,7 +262,7 @@ __global__ void __launch_bounds__(64) cw64_eval_kernel(const uint4 *__restrict__
         }
         case O_ASSERT_EQ: fail = a != b; break;
         case O_ASSERT_NZ: fail = a == 0; break;
-        default: break;
+        default: d = gl_alu(op, a, b, &fail); break;
         }
         if (fail && !(st & 3u))                                      // the first failing check in program order
             st = (op == O_IDIV || op == O_MOD ? CW_ST_ARITH : CW_ST_ASSERT_FAILED) | (y.y << 8);
@@ -401,10 +516,18 @@ hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t i
     }
     return hipSuccess;
 }
+// calls: 0 = no O_CALL row in the program, 1 = register windows in the table, 2 = in LDS (lds_bytes = 512 x the registers of the
+// largest function, at most 64 KiB: what a launch gets as dynamic LDS without a function attribute)
 hipError_t cwk64_eval(hipStream_t s, const void *rows, uint32_t n_rows, const void *consts, void *V, uint32_t Bp, uint32_t batch,
-                      uint32_t *status) {
-    hipLaunchKernelGGL(cw64_eval_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, (const uint4 *)rows, n_rows, (const uint64_t *)consts,
-                       (uint64_t *)V, Bp, batch, status);
+                      uint32_t *status, const void *ftab, const void *fcode, uint32_t calls, uint32_t lds_bytes) {
+    if (calls > 2 || (calls == 2 ? lds_bytes == 0 || lds_bytes > 65536u : lds_bytes != 0)) return hipErrorInvalidValue;
+    const dim3 grid((batch + 63) / 64);
+#define CW64_EVAL(C) hipLaunchKernelGGL(cw64_eval_kernel<C>, grid, dim3(64), lds_bytes, s, (const uint4 *)rows, n_rows, (const uint64_t *)consts, \
+                                        (uint64_t *)V, Bp, batch, status, (const uint4 *)ftab, (const uint4 *)fcode)
+    if (calls == 0) CW64_EVAL(0);
+    else if (calls == 1) CW64_EVAL(1);
+    else CW64_EVAL(2);
+#undef CW64_EVAL
     return hipGetLastError();
 }
 hipError_t cwk64_r1cs(hipStream_t s, const void *chunks, uint32_t n_chunks, const void *terms, const void *V, uint32_t Bp, uint32_t batch,

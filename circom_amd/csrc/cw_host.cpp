@@ -21,6 +21,7 @@
 #include "cw_bits_host.h"
 #include "cw_devbuf.h"
 #include "cw_rerun.h"
+#include "cw_fn64.h"
 
 typedef unsigned __int128 u128;
 
@@ -311,6 +312,7 @@ struct cw_circuit {
     std::vector<uint32_t> rows64;          // n_rows * 8
     std::vector<uint64_t> consts64;
     uint32_t n_slots64 = 0;
+    uint32_t fn_max_regs64 = 0;            // registers of its largest run-time function (fn_tab / fn_code hold them: cw_fn64.h), 0 = none
     std::vector<uint32_t> r1_terms64;      // R1CS terms {slot, part | end << 2, coefficient lo, hi}
     std::vector<uint32_t> r1_chunks64;     // chunks of consecutive constraints {first term, terms, first row, 0}: one workgroup each
     bool has_jit = false;
@@ -507,10 +509,52 @@ static const char *validate_pipe_variant(const Variant &v, uint32_t n_signals, u
     return nullptr;
 }
 
+// the log program of a tape (both engines): n_log_statements x { u32 flat operation that ends the statement | u32 n_items | items }
+static int load_log_program(cw_circuit *c, const std::vector<uint8_t> &b, size_t &off, uint32_t n_log_statements) {
+    uint32_t seen = 0;
+    for (uint32_t li = 0; li < n_log_statements; li++) {
+        if (off + 8 > b.size()) return fail(CW_EIO, "tape log program truncated");
+        uint32_t lh[2];
+        memcpy(lh, b.data() + off, 8);
+        off += 8;
+        cw_circuit::LogStmt st;
+        st.at = lh[0];
+        if (lh[1] > (1u << 16) || (!c->logs.empty() && st.at <= c->logs.back().at)) return fail(CW_EIO, "tape log program: bad statement");
+        for (uint32_t k = 0; k < lh[1]; k++) {
+            if (off + 8 > b.size()) return fail(CW_EIO, "tape log program truncated");
+            uint32_t ih[2];
+            memcpy(ih, b.data() + off, 8);
+            off += 8;
+            cw_circuit::LogItem it;
+            if (ih[0] == 0) {
+                if (ih[1] > b.size() - off) return fail(CW_EIO, "tape log program truncated");
+                it.text.assign((const char *)b.data() + off, ih[1]);
+                off += ih[1];
+            } else if (ih[0] == 1 && ih[1] == seen) {       // values are numbered in statement order
+                it.is_value = true;
+                it.value = ih[1];
+                seen++;
+            } else return fail(CW_EIO, "tape log program: bad item");
+            st.items.push_back(std::move(it));
+        }
+        c->logs.push_back(std::move(st));
+    }
+    if (seen != c->n_logv) return fail(CW_EIO, "tape log program: value count differs from the header");
+    return CW_OK;
+}
+
 // ---- the 64-bit runtime's tape ("CW64", hip_elements/lower64.py) ------------------------------------------------------------
-//   "CW64" | u32 version = 1 | u64 prime | 12 x u32: n_signals, n_witness, n_consts, input_start, n_inputs, n_input_names,
-//   hashmap_size, n_public_inputs, n_slots, n_rows, io-map templates in the .dat, 0 | consts n_consts x u64 | witness2signal
-//   n_witness x u32 | input names { u32 len | bytes | u32 start | u32 size } | rows n_rows x 8 x u32 (cw64.hip)
+//   "CW64" | u32 version = 1 | 2 | u64 prime | 12 x u32: n_signals, n_witness, n_consts, input_start, n_inputs, n_input_names,
+//   hashmap_size, n_public_inputs, n_slots, n_rows, io-map templates in the .dat, n_logv (version 1: 0) | consts n_consts x u64 |
+//   witness2signal n_witness x u32 | input names { u32 len | bytes | u32 start | u32 size } |
+//   version 2 only: functions (cw_fn64.h: u32 n_functions | per function { u32 n_regs | u32 n_ins | n_ins x 4 x u32 }) |
+//                   log program (u32 n_statements | per statement { u32 flat operation that ends it | u32 n_items | items: u32 0 |
+//                   u32 len | bytes, or u32 1 | u32 j }: the items of the 256-bit tape) |
+//   rows n_rows x 8 x u32 (cw64.hip), to the end of the file
+//   Version 1 = a circuit with neither run-time functions nor log statements (rows: op <= 26).  Version 2: the n_logv slots behind
+//   the circuit's signals hold the arguments of the log statements (hidden: no witness entry names them, cw_n_signals does not
+//   count them, c->n_signals does - the 256-bit loader's convention, which cw_get_log and cw_get_signal rely on); a row may be
+//   O_CALL (27): a = function id, b = first slot of its register window, which lies among the temporaries.
 static const uint64_t GOLDILOCKS = 0xFFFFFFFF00000001ull;
 static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
     if (b.size() < 16 + 48) return fail(CW_EIO, "tape file truncated");
@@ -518,7 +562,7 @@ static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
     memcpy(&ver, b.data() + 4, 4);
     uint64_t prime;
     memcpy(&prime, b.data() + 8, 8);
-    if (ver != 1) return fail(CW_EIO, "unsupported 64-bit tape version");
+    if (ver != 1 && ver != 2) return fail(CW_EIO, "unsupported 64-bit tape version");
     if (prime != GOLDILOCKS) return fail(CW_EIO, "the 64-bit runtime serves the Goldilocks prime only");
     c->is64 = true;
     c->q = U256{{prime, 0, 0, 0}};
@@ -536,7 +580,8 @@ static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
     const uint32_t n_rows = m[9];
     c->n_dat_consts = 0;                                       // the 64-bit .dat carries no constants (c_code_generator.rs:838-841)
     c->n_io_templates = m[10];
-    if (c->n_signals == 0 || c->n_signals >= (1u << 26) || c->n_slots64 < c->n_signals || c->n_slots64 >= (1u << 28) || m[11] ||
+    if (c->n_signals == 0 || c->n_signals >= (1u << 26) || c->n_slots64 < c->n_signals || c->n_slots64 >= (1u << 28) || (ver == 1 && m[11]) ||
+        m[11] > c->n_slots64 - c->n_signals ||
         c->input_start == 0 || (uint64_t)c->input_start + c->n_inputs > c->n_signals || c->n_pub_in > c->n_inputs || c->n_witness == 0 ||
         c->n_witness > c->n_signals || hsize < 256 || (hsize & (hsize - 1)) || n_names > hsize || n_names > c->n_inputs + 1u ||
         n_rows > (1u << 26) || c->n_consts > (1u << 26) || c->n_io_templates > (1u << 20))
@@ -551,7 +596,7 @@ static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
     memcpy(c->w2s.data(), b.data() + off, (size_t)c->n_witness * 4);
     off += (size_t)c->n_witness * 4;
     for (uint32_t v : c->w2s)
-        if (v >= c->n_signals) return fail(CW_EIO, "tape witness list refers to a signal out of range");
+        if (v >= c->n_signals) return fail(CW_EIO, "tape witness list refers to a signal out of range");     // (n_logv is added below)
     for (uint32_t i = 0; i < n_names; i++) {
         if (off + 4 > b.size()) return fail(CW_EIO, "tape input names truncated");
         uint32_t len;
@@ -566,6 +611,24 @@ static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
         if (ss[0] < c->input_start || (uint64_t)ss[0] + ss[1] > (uint64_t)c->input_start + c->n_inputs) return fail(CW_EIO, "tape input name outside the main inputs");
         if (!c->input_names.emplace(nm, std::make_pair(ss[0], ss[1])).second) return fail(CW_EIO, "tape input name appears twice");
     }
+    c->n_logv = m[11];
+    c->n_signals += c->n_logv;                                 // hidden log values behind the circuit's signals
+    if (ver == 2) {
+        CwFn64 fns;
+        size_t used = 0;
+        if (const char *why = cw_fn64_parse(b.data() + off, b.size() - off, c->n_consts, &fns, &used))
+            return fail(CW_EIO, std::string("64-bit tape: ") + why);
+        off += used;
+        c->fn_tab = std::move(fns.tab);
+        c->fn_code = std::move(fns.code);
+        c->fn_max_regs64 = fns.max_regs;
+        if (off + 4 > b.size()) return fail(CW_EIO, "tape log program truncated");
+        uint32_t n_log_statements;
+        memcpy(&n_log_statements, b.data() + off, 4);
+        off += 4;
+        if (n_log_statements > (1u << 20)) return fail(CW_EIO, "tape log program: bad statement");
+        if (int rc = load_log_program(c, b, off, n_log_statements)) return rc;
+    }
     if (b.size() - off != (size_t)n_rows * 32) return fail(CW_EIO, "64-bit tape: row section size");
     c->rows64.resize((size_t)n_rows * 8);
     memcpy(c->rows64.data(), b.data() + off, (size_t)n_rows * 32);
@@ -575,6 +638,11 @@ static int load_tape64(cw_circuit *c, const std::vector<uint8_t> &b) {
         const uint32_t vs[3] = {w[2], w[3], w[4]};
         bool ok = op <= 26 && !(w[0] >> 16) && (dk == 3 || (dk == 0 && w[1] > 0 && w[1] < c->n_slots64));
         for (int j = 0; j < 3; j++) ok = ok && (ks[j] == 3 || (ks[j] == 0 && vs[j] < c->n_slots64) || (ks[j] == 2 && vs[j] < c->n_consts));
+        if (ver == 2 && op == CW64_O_CALL) {                   // the window = n_regs temporaries from slot b on
+            const uint32_t n_fn = (uint32_t)(c->fn_tab.size() / 4);
+            ok = !(w[0] >> 16) && dk == 3 && ks[0] == 3 && ks[1] == 0 && ks[2] == 3 && w[2] < n_fn && w[3] >= c->n_signals &&
+                 w[3] < c->n_slots64 && c->fn_tab[(size_t)w[2] * 4 + 2] <= c->n_slots64 - w[3];
+        }
         if (!ok) return fail(CW_EIO, "64-bit tape: bad row");
     }
     c->n_rows = n_rows;
@@ -824,37 +892,7 @@ static int load_tape(cw_circuit *c, const char *path) {
         }
     }
     // log statements: strings and references to the hidden signals
-    {
-        uint32_t seen = 0;
-        for (uint32_t li = 0; li < n_log_statements; li++) {
-            if (off + 8 > b.size()) return fail(CW_EIO, "tape log program truncated");
-            uint32_t lh[2];
-            memcpy(lh, b.data() + off, 8);
-            off += 8;
-            cw_circuit::LogStmt st;
-            st.at = lh[0];
-            if (lh[1] > (1u << 16) || (!c->logs.empty() && st.at <= c->logs.back().at)) return fail(CW_EIO, "tape log program: bad statement");
-            for (uint32_t k = 0; k < lh[1]; k++) {
-                if (off + 8 > b.size()) return fail(CW_EIO, "tape log program truncated");
-                uint32_t ih[2];
-                memcpy(ih, b.data() + off, 8);
-                off += 8;
-                cw_circuit::LogItem it;
-                if (ih[0] == 0) {
-                    if (ih[1] > b.size() - off) return fail(CW_EIO, "tape log program truncated");
-                    it.text.assign((const char *)b.data() + off, ih[1]);
-                    off += ih[1];
-                } else if (ih[0] == 1 && ih[1] == seen) {       // values are numbered in statement order
-                    it.is_value = true;
-                    it.value = ih[1];
-                    seen++;
-                } else return fail(CW_EIO, "tape log program: bad item");
-                st.items.push_back(std::move(it));
-            }
-            c->logs.push_back(std::move(st));
-        }
-        if (seen != c->n_logv) return fail(CW_EIO, "tape log program: value count differs from the header");
-    }
+    if (int rc = load_log_program(c, b, off, n_log_statements)) return rc;
     if (n_variants == 0) return fail(CW_EIO, "tape holds no schedule");
     for (uint32_t v = 0; v < n_variants; v++) {
         if (off + 32 > b.size()) return fail(CW_EIO, "tape variant truncated");
@@ -1732,6 +1770,9 @@ struct cw_batch {
     // 64-bit runtime: V64[slot][Bp], its program and R1CS terms
     DevBuf<uint64_t> d_V64, d_consts64;
     DevBuf<uint32_t> d_rows64, d_terms64, d_chunks64;
+    DevBuf<uint32_t> d_ftab64, d_fcode64;              // run-time functions (cw_fn64.h): table and bytecode
+    uint32_t calls64 = 0;                              // cwk64_eval's `calls`: 0 = the circuit has no function, 1 = windows in the table, 2 = in LDS
+    uint32_t call_lds = 0;                             // bytes of LDS per workgroup for the windows (calls64 == 2), else 0
     bool egress_tiled = true;                          // CW64_EGRESS_TILED=0: the 32-byte bulk forms go through cw64_gather_kernel (A/B timing)
     int ingest_tiled = -1;                             // CW64_INGEST_TILED: 0 = cw64_ingest_kernel, 1 = the tiled kernel, unset = by input count
     uint32_t in_eb = 32;                               // element bytes of the current bulk inputs (d_in / ext_in): 8 after cw_set_inputs*_n8
@@ -2561,6 +2602,17 @@ extern "C" int cw_set_inputs_json(cw_batch *b, uint32_t instance, const char *js
 // widths; nothing was measured between 16 and 64.  ONE threshold for both widths on purpose: the 8-byte form already wins at 16
 // inputs (by less than a tenth), the 32-byte form does not, and a second constant for that is not worth its test.
 static const uint32_t CW64_INGEST_TILE_MIN = 64;
+// Register windows of run-time functions (cw64.hip cw64_call).  The LDS placement CAN hold functions of up to
+// CW64_CALL_LDS_MAX_REGS = 128 registers: 128 x 512 bytes = 64 KiB, what a launch gets as dynamic LDS without a function attribute.
+// It is USED, unless CW64_CALL_LDS says otherwise, up to CW64_CALL_LDS_AUTO_REGS = 10: 5 KiB per one-wave workgroup, the largest
+// window with which the CU's 160 KiB of LDS still hold the 32 waves its registers allow (8 per SIMD), so LDS never lowers the
+// residency.  Measured (tools/ubench_call64.py, profiles/call64_*.json, the table at the top of NOTES.md): at 10 registers LDS is
+// 3 % faster than the table at 1 024 and 65 536 instances and level with it at 2^20.  Larger windows win the same 2 .. 3 % while
+// every workgroup of the batch is resident anyway (32, 48, 64 registers at 65 536 instances = 4 workgroups per CU) and lose as soon
+// as LDS caps the residency: +59 % at 118 registers x 65 536, +57 % / +104 % / +178 % at 32 / 48 / 64 registers x 2^20.
+// CW64_CALL_LDS = 0 / 1, read when the batch is created, forces a placement (1 is ignored above CW64_CALL_LDS_MAX_REGS).
+static const uint32_t CW64_CALL_LDS_MAX_REGS = 128;
+static const uint32_t CW64_CALL_LDS_AUTO_REGS = 10;
 static int batch_setup64(cw_batch *b) {
     cw_circuit *c = b->c;
     b->v_bytes = (size_t)c->n_slots64 * b->Bp * 8;
@@ -2579,6 +2631,14 @@ static int batch_setup64(cw_batch *b) {
     HIPCHK(b->d_gather.alloc(std::max<size_t>((size_t)c->n_witness * 32, 32)));
     if (const char *e = getenv("CW64_EGRESS_TILED")) b->egress_tiled = atoi(e) != 0;
     if (const char *e = getenv("CW64_INGEST_TILED")) b->ingest_tiled = atoi(e) != 0;
+    if (c->fn_max_regs64) {
+        HIPCHK(upload(&b->d_ftab64, c->fn_tab, b->stream));
+        HIPCHK(upload(&b->d_fcode64, c->fn_code, b->stream));
+        bool lds = c->fn_max_regs64 <= CW64_CALL_LDS_AUTO_REGS;
+        if (const char *e = getenv("CW64_CALL_LDS")) lds = atoi(e) != 0 && c->fn_max_regs64 <= CW64_CALL_LDS_MAX_REGS;
+        b->calls64 = lds ? 2 : 1;
+        b->call_lds = lds ? c->fn_max_regs64 * 512u : 0;
+    }
     HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
     HIPCHK(hipStreamSynchronize(b->stream));
     return CW_OK;
@@ -2786,7 +2846,8 @@ extern "C" int cw_run(cw_batch *b) {
         else
             HIPCHK(cwk64_ingest(b->stream, in, b->d_V64, c->input_start, c->n_inputs, b->batch, b->Bp, b->in_eb));
         TMARK(b, 1);
-        HIPCHK(cwk64_eval(b->stream, b->d_rows64, (uint32_t)(c->rows64.size() / 8), b->d_consts64, b->d_V64, b->Bp, b->batch, b->d_status));
+        HIPCHK(cwk64_eval(b->stream, b->d_rows64, (uint32_t)(c->rows64.size() / 8), b->d_consts64, b->d_V64, b->Bp, b->batch, b->d_status,
+                          b->d_ftab64, b->d_fcode64, b->calls64, b->call_lds));
         TMARK(b, 2);
         b->ran = true;
         return CW_OK;
@@ -3164,6 +3225,7 @@ static int get_witnesses_host(cw_batch *b, uint32_t first, uint32_t count, uint8
     return CW_OK;
 }
 extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) { return get_witnesses_host(b, first, count, out, 32); }
+extern "C" uint32_t cw_batch_call_lds(const cw_batch *b) { return b ? b->call_lds : 0; }
 extern "C" uint32_t cw_element_bytes(const cw_circuit *c) { return c && c->is64 ? 8 : 32; }
 
 // Device-side form for GPU provers: canonical 32-byte values of `count` instances written to DEVICE memory
@@ -3553,6 +3615,7 @@ extern "C" void *cw_device_values(cw_batch *b, uint64_t *n_bytes, uint32_t *padd
     }
     if (n_bytes) *n_bytes = b->v_bytes;
     if (padded_batch) *padded_batch = b->Bp;
+    if (b->c->is64) return b->d_V64;        // V[slot][padded batch] of uint64: signals, hidden log values, temporaries
     return b->d_V;
 }
 

@@ -65,8 +65,10 @@ hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_s
                         uint32_t elem_bytes);
 hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
                               uint32_t elem_bytes);
+// calls: 0 = no O_CALL row in the program (ftab / fcode unused), 1 = register windows of run-time functions in the value table,
+// 2 = in LDS, lds_bytes = 512 x the registers of the largest function (<= 64 KiB); ftab / fcode: cw_fn64.h
 hipError_t cwk64_eval(hipStream_t s, const void *rows, uint32_t n_rows, const void *consts, void *V, uint32_t Bp, uint32_t batch,
-                      uint32_t *status);
+                      uint32_t *status, const void *ftab, const void *fcode, uint32_t calls, uint32_t lds_bytes);
 hipError_t cwk64_r1cs(hipStream_t s, const void *chunks, uint32_t n_chunks, const void *terms, const void *V, uint32_t Bp, uint32_t batch,
                       uint32_t *status, uint32_t *first_bad);
 hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,

@@ -31,7 +31,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_fn64.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -102,6 +102,7 @@ _SIGS = {
     "cw_get_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_get_witnesses_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_element_bytes": (C.c_uint32, [C.c_void_p]),
+    "cw_batch_call_lds": (C.c_uint32, [C.c_void_p]),
     "cw_get_public": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_public_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_signal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
@@ -242,6 +243,7 @@ class Batch:
         self.emitted = bool(em)              # the variant's rows run as emitted code (hip_elements/fpjit.py)
         self.fused_check = em == 2           # ... which also recomputes the R1CS rows it covers
         self.bitmode = bool(lib().cw_batch_bitmode(h))
+        self.call_lds = lib().cw_batch_call_lds(h)      # 64-bit runtime: bytes of LDS per workgroup for function register windows (0: table / none)
         lay = (C.c_uint64 * 4)()
         _chk(lib().cw_batch_bits_layout(h, lay))
         # bit table of this batch: element (group g, slot s) = T[(((g >> sh) * slots + s) << sh) + (g & ((1 << sh) - 1))]
@@ -402,6 +404,12 @@ class Batch:
         """the same with the element of the .wtns files ([count][n_witness][circuit.element_bytes]): 8 bytes per value for
         circuits of the 64-bit runtime, witnesses_device for every other"""
         _chk(lib().cw_get_witnesses_device_n8(self.h, first, count, C.c_void_p(d_ptr)))
+
+    def device_values(self):
+        """(device pointer, bytes, padded batch) of the value table (cw_device_values; layout: include/circom_amd.h)"""
+        n, bp = C.c_uint64(), C.c_uint32()
+        p = lib().cw_device_values(self.h, C.byref(n), C.byref(bp))
+        return p, n.value, bp.value
 
     def signal(self, instance: int, slot: int) -> int:
         buf = C.create_string_buffer(32)

@@ -89,6 +89,12 @@ void cw_prime(const cw_circuit *c, uint8_t le32[32]); /* Fr_q (fr.hpp) */
 /* n8 of the circuit's .wtns files (writeBinWitness: the prime's byte length): 8 for circuits of the 64-bit runtime
  * (--prime goldilocks, common64/main.cpp), 32 otherwise */
 uint32_t cw_element_bytes(const cw_circuit *c);
+/* 64-bit runtime, circuits that call run-time functions (loops, branches, array indices that depend on values): bytes of LDS
+ * per workgroup that hold the functions' register windows; 0 = the windows live in the value table, or the circuit has no such
+ * function.  LDS is used when no function needs more than 10 registers - the largest window that never lowers the number of
+ * resident waves; the measurements are in NOTES.md.  CW64_CALL_LDS=0 / 1 in the environment of cw_batch_create forces a
+ * placement (1 is ignored above 128 registers: 64 KiB).  Both placements compute the same table. */
+uint32_t cw_batch_call_lds(const cw_batch *b);
 /* getInputSignalSize(h) (calcwit.cpp:99-102): size of input `name`, or -1 */
 int64_t cw_input_size(const cw_circuit *c, const char *name, uint32_t *start_slot);
 
@@ -247,7 +253,8 @@ int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, char *out, 
  * and a newline per statement).  A batched run has no console per instance: the schedule keeps every logged value in
  * the table (hidden signals behind the circuit's own; cw_n_signals does not count them) and cw_get_log formats what the
  * reference binary prints on stdout for ONE instance, up to its first failed run-time check (where the reference process
- * exits).  Returns the length of the text or a negative CW_E* code; stores at most out_len - 1 characters + NUL. */
+ * exits).  Returns the length of the text or a negative CW_E* code; stores at most out_len - 1 characters + NUL.
+ * Both engines serve it: circuits of the 64-bit runtime (--prime goldilocks) keep their logged values in hidden 8-byte slots. */
 uint32_t cw_n_log_statements(const cw_circuit *c);
 int64_t cw_get_log(cw_batch *b, uint32_t instance, char *out, size_t out_len);
 /* first violated constraint per instance after cw_check_r1cs: [batch], 0xFFFFFFFF = none */
@@ -267,7 +274,9 @@ int cw_r1cs_stream_plan(const cw_circuit *c, uint32_t terms_per_chunk, uint32_t 
 /* raw device pointers for zero-copy consumers (provers): value table, layout in DESIGN.md.  When cw_circuit_montgomery()
    is 1 the table holds x * 2^261 mod q (the schedule of an arithmetic circuit keeps its signals in Montgomery form, so that
    a product of two signals is one Montgomery product); every other egress (cw_get_witness*, cw_get_signal, cw_write_wtns*,
-   cw_get_witnesses_device) returns canonical values, as the reference's Fr_toLongNormal does (main.cpp:326-332). */
+   cw_get_witnesses_device) returns canonical values, as the reference's Fr_toLongNormal does (main.cpp:326-332).
+   64-bit runtime (--prime goldilocks): V[slot][padded batch] of uint64 canonical residues - slot 0 = the constant 1, the
+   circuit's signals, the hidden log values, then the temporaries (csrc/cw64.hip). */
 void *cw_device_values(cw_batch *b, uint64_t *n_bytes, uint32_t *padded_batch);
 int cw_circuit_montgomery(const cw_circuit *c);
 /* bit-plane batches: the bit table T[group][slot] (uint64, bit i = instance group*64+i).  Slot 0 / 1 = the constants
