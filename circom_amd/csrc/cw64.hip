@@ -477,6 +477,114 @@ __global__ void __launch_bounds__(256) cw64_ingest_tiled_kernel(const uint8_t *_
         if (lane < nj) V[(size_t)(input_start + k0 + k) * Bp + j0 + lane] = tile[k * EG_S + lane];
 }
 
+// Supplied witnesses (cw_set_witnesses*, cw_read_wtns*): the mirror image of cw64_egress_kernel.  [count][n_wit][EB] bytes, EB = 8
+// (this runtime's .wtns element) or 32 (the boundary's), entry k of instance j into V[w2s[k]][first + j].  The transpose is the
+// one of cw64_ingest_tiled_kernel above - same work distribution (a workgroup of four waves owns 64 instances x EG_T entries),
+// same loads in one straight-line block, same reduction, the same 65-word tile written column-wise and read row-wise, so the
+// bank arithmetic of the comment above that kernel holds here word for word - with two differences:
+//   write   the slot of entry k0 + k is w2s[k0 + k], not input_start + k0 + k: wave-uniform, a scalar load with the index
+//           clamped to the list as the egress kernel clamps it, the 16 loads of a wave ahead of its 16 stores of 512 bytes.
+//           Entry 0 is NOT stored: slot 0 keeps the 1 of cw64_init_kernel, so that the constant terms of the R1CS check stay
+//           meaningful for the other wires of a witness whose entry 0 is wrong.
+//   check   a checker must not quietly repair what it is given.  The reduced value is stored (the check cannot run without
+//           one), and CW_ST_BAD_WITNESS is or'ed into status[first + j] when a value of instance j was not canonical (8-byte
+//           form: >= p; 32-byte form: word 0 >= p or any of words 1..3 set) or its entry 0 is not 1.  On the read side a WAVE
+//           holds one instance's row of the tile per load: one ballot per load (the 32-byte form's is the ballot that skips the
+//           long reduction) sets bit i of a wave-uniform mask, i = the wave's i-th instance, and lane i issues the atomicOr -
+//           at most 16 per wave, none for well-formed witnesses.  Another workgroup may report the same instance for another
+//           entry tile: or is idempotent.
+// Lanes past `count` and entries past n_wit neither read nor write (their registers stay 0, which no test above flags - the
+// entry-0 test is under the row's own condition); nothing is read past the end of the image.  `first` need not be a multiple
+// of 64: a row of V is 8-byte aligned wherever it starts.  `in`: 8-byte aligned (EB = 8), 16-byte aligned (EB = 32).
+template <int EB>
+__global__ void __launch_bounds__(256) cw64_wit_ingest_kernel(const uint8_t *__restrict__ in, uint64_t *__restrict__ V,
+                                                              const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
+                                                              uint32_t count, uint32_t *status) {
+    __shared__ uint64_t tile[EG_T * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
+    const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool entry0 = k0 == 0 && lane == 0;                          // this lane's (first) piece is the head of entry 0
+    uint32_t badmask = 0;                                              // bit i: instance wave + 4 i of the tile is malformed (wave-uniform)
+    if (EB == 8) {
+        const uint64_t *t0 = (const uint64_t *)in + (size_t)j0 * n_wit + k0;
+        uint64_t v[64 / 4] = {};
+        if (lane < nk) {
+            if (nj == 64u) {
+#pragma unroll
+                for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * n_wit + lane];
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 64 / 4; i++)
+                    if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * n_wit + lane];
+            }
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 64 / 4; i++) {
+            const bool bad = v[i] >= GL_P || (entry0 && wave + 4 * i < nj && v[i] != 1);
+            if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+            tile[lane * EG_S + wave + 4 * i] = gl_wrap(v[i]);
+        }
+    } else {
+        const uint4 *t0 = (const uint4 *)in + ((size_t)j0 * n_wit + k0) * 2;
+        const bool odd = lane & 1u;
+        uint4 v[64 / 4][2] = {};
+        if (nj == 64u && nk == EG_T) {                                 // a full tile: all 32 loads of the wave in one block
+#pragma unroll
+            for (uint32_t i = 0; i < 64 / 4; i++) {
+                v[i][0] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane];
+                v[i][1] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64];
+            }
+        } else
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {
+            if (((lane + 64 * h) >> 1) < nk) {
+                if (nj == 64u) {
+#pragma unroll
+                    for (uint32_t i = 0; i < 64 / 4; i++) v[i][h] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64 * h];
+                } else {
+#pragma unroll
+                    for (uint32_t i = 0; i < 64 / 4; i++)
+                        if (wave + 4 * i < nj) v[i][h] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64 * h];
+                }
+            }
+        }
+        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2 (mod p)
+        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e);
+#pragma unroll
+        for (uint32_t i = 0; i < 64 / 4; i++) {
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint64_t lo = ((uint64_t)v[i][h].y << 32) | v[i][h].x, hi = ((uint64_t)v[i][h].w << 32) | v[i][h].z;
+                uint64_t r = gl_wrap(lo);
+                if (__builtin_amdgcn_ballot_w64(odd ? (lo | hi) != 0 : hi != 0)) {         // words 1..3 set: malformed, and the long form
+                    badmask |= 1u << i;
+                    uint64_t part = gl_add(r, gl_mul(gl_wrap(hi), e));
+                    if (odd) part = gl_mul(part, e2);
+                    r = gl_add(part, (uint64_t)__shfl_xor((unsigned long long)part, 1));
+                }
+                const bool bad = !odd && (lo >= GL_P || (h == 0 && entry0 && wave + 4 * i < nj && lo != 1));
+                if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+                if (!odd) tile[((lane >> 1) + 32 * h) * EG_S + wave + 4 * i] = r;
+            }
+        }
+    }
+    if (lane < 64 / 4 && ((badmask >> lane) & 1u)) atomicOr(&status[first + j0 + wave + 4 * lane], CW_ST_BAD_WITNESS);
+    __syncthreads();
+    uint64_t *Vj = V + first + j0 + lane;
+    uint32_t slot[EG_T / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        const uint32_t k = wave + 4 * i;
+        slot[i] = w2s[k < nk ? k0 + k : k0];                         // always an entry of the list: the scalar load needs no branch
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        const uint32_t k = wave + 4 * i;
+        if (k < nk && k0 + k != 0 && lane < nj) Vj[(size_t)slot[i] * Bp] = tile[k * EG_S + lane];
+    }
+}
+
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 hipError_t cwk64_init(hipStream_t s, void *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad) {
     hipLaunchKernelGGL(cw64_init_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, (uint64_t *)V, Bp, status, first_bad);
@@ -513,6 +621,27 @@ hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t i
         else
             hipLaunchKernelGGL(cw64_ingest_tiled_kernel<32>, grid, dim3(256), 0, s, i, v, input_start, n_in, n, Bp);
         if (hipError_t e = hipGetLastError()) return e;              // nothing more is launched behind a launch that failed
+    }
+    return hipSuccess;
+}
+// supplied witnesses [count][n_wit][elem_bytes] into the columns first .. first + count of V; elem_bytes = 8 (`in` 8-byte aligned)
+// or 32 (16-byte aligned); instance tiles split over launches of 65 535 as cwk64_egress splits them, and nothing more is
+// launched behind a launch that failed
+hipError_t cwk64_wit_ingest(hipStream_t s, const void *in, void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
+                            uint32_t count, uint32_t *status, uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if ((uintptr_t)in & (elem_bytes == 32 ? 15 : 7)) return hipErrorInvalidValue;
+    if (!n_wit || !count) return hipSuccess;
+    const uint32_t per = 65535u * 64u;
+    for (uint32_t done = 0; done < count; done += per) {
+        const uint32_t n = count - done < per ? count - done : per;
+        const dim3 grid((n_wit + EG_T - 1) / EG_T, (n + 63) / 64);
+        const uint8_t *i = (const uint8_t *)in + (size_t)done * n_wit * elem_bytes;
+        if (elem_bytes == 8)
+            hipLaunchKernelGGL(cw64_wit_ingest_kernel<8>, grid, dim3(256), 0, s, i, (uint64_t *)V, w2s, n_wit, Bp, first + done, n, status);
+        else
+            hipLaunchKernelGGL(cw64_wit_ingest_kernel<32>, grid, dim3(256), 0, s, i, (uint64_t *)V, w2s, n_wit, Bp, first + done, n, status);
+        if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
 }

@@ -3,6 +3,11 @@
 //     here:        cw_witness <name> <input.json> <output.wtns>        one instance, same files, same .wtns bytes
 //                  cw_witness <name> <inputs.json> <out_%d.wtns>       inputs.json = JSON ARRAY of input objects:
 //                                                                      one batch on the GPU, one .wtns per instance
+//                  cw_witness --check <name> <a.wtns> [<b.wtns> ...]   witnesses IN (64-bit runtime): the files of any calculator
+//                                                                      checked against <name>.r1cs in one batch, one line per
+//                                                                      file: OK | MALFORMED | constraint <row> violated (+ the
+//                                                                      wires by name when <name>.sym exists); exit 0 = all OK,
+//                                                                      1 = some file is not, 2 = usage, I/O, another runtime
 // <name> is the path prefix of <name>.cwt / <name>.dat / <name>.r1cs (the .r1cs is optional: without it the
 // constraint check is skipped).  Exit code 0 = every instance produced a witness; 1 = at least one failed (the
 // reference aborts on the first failed assert, calcwit/assert_bucket.rs:75-77; here the others are still written).
@@ -60,7 +65,54 @@ static std::vector<std::string> elements(const std::string &t) {
         if (rc_ != CW_OK) { fprintf(stderr, "%s: %s\n", #call, cw_last_error()); return 2; } \
     } while (0)
 
+// the batch counterpart of `snarkjs wtns check`: files[i] becomes instance i
+static int check_files(const std::string &name, char **files, uint32_t n) {
+    cw_circuit *c = nullptr;
+    CHECK(cw_load((name + ".cwt").c_str(), (name + ".dat").c_str(), (name + ".r1cs").c_str(), &c));
+    if (FILE *wl = fopen((name + ".w2s").c_str(), "rb")) {           // the witness list of a simplified system, as below
+        std::vector<uint32_t> list;
+        uint32_t v;
+        while (fread(&v, 4, 1, wl) == 1) list.push_back(v);
+        fclose(wl);
+        if (!list.empty()) CHECK(cw_set_witness_list(c, list.data(), (uint32_t)list.size()));
+    }
+    const std::string sym = name + ".sym";
+    FILE *sp = fopen(sym.c_str(), "rb");
+    if (sp) fclose(sp);
+    const int device = getenv("CW_DEVICE") ? atoi(getenv("CW_DEVICE")) : 0;
+    cw_batch *b = nullptr;
+    CHECK(cw_batch_create(c, device, n, nullptr, &b));
+    for (uint32_t i = 0; i < n; i++) CHECK(cw_read_wtns(b, i, files[i]));
+    CHECK(cw_check_r1cs(b));
+    CHECK(cw_sync(b));
+    std::vector<uint32_t> st(n), row(n);
+    CHECK(cw_get_status(b, st.data()));
+    CHECK(cw_get_r1cs_first_bad(b, row.data()));
+    int bad = 0;
+    std::vector<char> text(1 << 16);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!st[i]) { printf("%s: OK\n", files[i]); continue; }
+        bad++;
+        if (st[i] & 8u) { printf("%s: MALFORMED\n", files[i]); continue; }
+        printf("%s: constraint %u violated\n", files[i], row[i]);
+        if (sp) {
+            CHECK(cw_explain(b, i, sym.c_str(), text.data(), text.size()));
+            fputs(text.data(), stdout);
+        }
+    }
+    cw_batch_free(b);
+    cw_free(c);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--check")) {
+        if (argc < 4) {
+            fprintf(stderr, "Usage: %s --check <circuit path prefix> <a.wtns> [<b.wtns> ...]\n", argv[0]);
+            return 2;
+        }
+        return check_files(argv[2], argv + 3, (uint32_t)(argc - 3));
+    }
     if (argc != 4) {
         fprintf(stderr, "Usage: %s <circuit path prefix> <input.json> <output.wtns | out_%%d.wtns>\n", argv[0]);
         return 2;

@@ -22,6 +22,7 @@
 #include "cw_devbuf.h"
 #include "cw_rerun.h"
 #include "cw_fn64.h"
+#include "cw_wtns_read.h"
 
 typedef unsigned __int128 u128;
 
@@ -1740,6 +1741,12 @@ struct cw_batch {
     std::vector<uint8_t> assigned; // [batch][n_in] flags (inputSignalAssigned, calcwit.cpp:28-32)
     std::vector<uint32_t> remaining;
     bool all_set = false, host_dirty = false, ran = false;
+    // supplied witnesses (cw_set_witnesses*, cw_read_wtns*; 64-bit runtime): the table was filled by the caller, not by the witness
+    // program.  wit_cover: one bit per instance that has been supplied since the first supply; wit_missing: the zero bits among
+    // the batch's instances - what `remaining` is to the inputs
+    bool supplied = false;
+    std::vector<uint64_t> wit_cover;
+    uint32_t wit_missing = 0;
     // ---- bit-plane mode (cw_bits.hip): one bit per signal per instance instead of a 32-byte slot ----
     bool bitmode = false;
     DevBuf<uint64_t> d_T, d_fbmask;                 // bit table [groups][slots]; per-group mask of instances to re-run wide
@@ -2832,6 +2839,7 @@ extern "C" int cw_run(cw_batch *b) {
         HIPCHK(hipMemcpyAsync(b->d_in, b->h_in.data(), b->h_in.size(), hipMemcpyHostToDevice, b->stream));
         b->host_dirty = false;
     }
+    b->supplied = false;                                             // the init kernel below resets what a supply left in the table
     const void *in = input_image(b);
     if (c->is64) {
         TMARK(b, 0);
@@ -2977,6 +2985,8 @@ extern "C" int cw_check_r1cs(cw_batch *b) {
     NEED_DEVICE(b);
     if (!b->ran) return fail(CW_ESTATE, "cw_check_r1cs before cw_run");
     if (c->n_constraints == 0) return fail(CW_ESTATE, "no .r1cs was loaded for this circuit");
+    if (b->supplied && b->wit_missing)                               // the counterpart of "Not all inputs have been set"
+        return fail(CW_ESTATE, "witnesses missing for " + std::to_string(b->wit_missing) + " instances");
     HIPCHK(hipSetDevice(b->device));
     if (c->is64) {
         TMARK(b, 3);
@@ -3094,6 +3104,7 @@ extern "C" int cw_run_check(cw_batch *b) {
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipGraphLaunch(b->rc_graph, b->stream));
     b->ran = true;
+    b->supplied = false;                                  // the graph begins with the init and ingest kernels: it is a cw_run
     if (b->bitmode) {
         if (b->jit) b->table_dirty = false;
         b->resolved = false;
@@ -3295,6 +3306,9 @@ extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint
     if (!b || !out) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch || slot >= b->c->n_signals) return fail(CW_EINVAL, "instance or slot out of range");
     NEED_DEVICE(b);
+    if (b->supplied && !std::binary_search(b->c->w2s.begin(), b->c->w2s.end(), slot))
+        return fail(CW_ESTATE, "cw_get_signal: no witness program has run on this table (the witnesses were supplied): a signal the "
+                               "witness list does not name was never written");
     HIPCHK(hipSetDevice(b->device));
     if (b->c->is64) {
         memset(out, 0, 32);
@@ -3418,23 +3432,26 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
     return ok ? CW_OK : fail(CW_EIO, std::string("short write: ") + path);
 }
 
+// a file-name pattern of the _many calls: exactly one integer conversion, nothing else
+static int check_file_pattern(const char *pattern) {
+    int convs = 0;
+    for (const char *p = pattern; *p; p++)
+        if (*p == '%') {
+            if (p[1] == '%') { p++; continue; }
+            const char *q = p + 1;
+            while (*q >= '0' && *q <= '9') q++;
+            if (*q != 'u' && *q != 'd') return fail(CW_EINVAL, "pattern may only hold one %u / %d conversion");
+            convs++;
+        }
+    if (convs != 1) return fail(CW_EINVAL, "pattern must hold exactly one %u / %d conversion");
+    return CW_OK;
+}
 // Many instances -> many .wtns files (one bulk device transpose per 256 MiB instead of one gather per instance):
 // `pattern` is a printf pattern with one %u / %d (the instance number).  What a prover farm consumes.
 extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern) {
     if (!b || !pattern) return fail(CW_EINVAL, "null argument");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
-    {   // exactly one integer conversion, nothing else
-        int convs = 0;
-        for (const char *p = pattern; *p; p++)
-            if (*p == '%') {
-                if (p[1] == '%') { p++; continue; }
-                const char *q = p + 1;
-                while (*q >= '0' && *q <= '9') q++;
-                if (*q != 'u' && *q != 'd') return fail(CW_EINVAL, "pattern may only hold one %u / %d conversion");
-                convs++;
-            }
-        if (convs != 1) return fail(CW_EINVAL, "pattern must hold exactly one %u / %d conversion");
-    }
+    if (int rc = check_file_pattern(pattern)) return rc;
     cw_circuit *c = b->c;
     const uint32_t eb = cw_element_bytes(c);        // 8 for the 64-bit runtime: its rows leave the device as the files hold them
     const size_t row = (size_t)c->n_witness * eb;
@@ -3451,6 +3468,117 @@ extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, c
         }
     }
     return CW_OK;
+}
+
+// ---- supplied witnesses: witnesses IN (64-bit runtime) ----------------------------------------------------------------------
+// A batch becomes "has a table" a second way: the caller hands in witnesses computed elsewhere (another calculator's .wtns
+// files, an image streamed out earlier) and cw_check_r1cs / cw_explain / every egress work on them.  The image is
+// [count][n_witness][eb] in witness-list order and goes through cw64_wit_ingest_kernel (cw64.hip), the egress transpose the
+// other way, which also flags malformed witnesses (CW_ST_BAD_WITNESS).  State: the FIRST supply since creation or since the
+// last cw_run re-initialises status words, first-bad rows and slot 0 and clears the coverage record; later supplies only add
+// coverage (an instance supplied twice is overwritten and keeps a CW_ST_BAD_WITNESS bit it had); cw_run and cw_run_check start
+// with the init kernel, so they simply end the supplied state.
+// What every entry point checks first, in this order: arguments (CW_EINVAL), engine (CW_ESTATE), device - the file forms read
+// and check their files (CW_EIO) between the last two, so a host-only batch can tell a good file from a bad one.
+static int supply_args(cw_batch *b, uint32_t first, uint32_t count, const void *img, uint32_t align) {
+    if (!b || !img) return fail(CW_EINVAL, "null argument");
+    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
+    if ((uintptr_t)img & (align - 1))
+        return fail(CW_EINVAL, "the device image of supplied witnesses must be " + std::to_string(align) + "-byte aligned");
+    if (!b->c->is64) return fail(CW_ESTATE, "supplied witnesses are served by the 64-bit runtime only (--prime goldilocks)");
+    return CW_OK;
+}
+static int supply_ready(cw_batch *b, uint32_t first, uint32_t count, const void *img, uint32_t align) {
+    if (int rc = supply_args(b, first, count, img, align)) return rc;
+    NEED_DEVICE(b);
+    HIPCHK(hipSetDevice(b->device));
+    return CW_OK;
+}
+// one launch for [count] instances of a DEVICE image, in stream order; opens the supplied state if the batch is not in it
+static int supply_device(cw_batch *b, uint32_t first, uint32_t count, const void *d_img, uint32_t eb) {
+    if (!b->supplied) {
+        HIPCHK(cwk64_init(b->stream, b->d_V64, b->Bp, b->d_status, b->d_first_bad));
+        b->wit_cover.assign((b->batch + 63) / 64, 0);
+        b->wit_missing = b->batch;
+        b->supplied = b->ran = true;
+    }
+    HIPCHK(cwk64_wit_ingest(b->stream, d_img, b->d_V64, b->d_w2s, b->c->n_witness, b->Bp, first, count, b->d_status, eb));
+    for (uint32_t i = first; i < first + count; i++) {
+        uint64_t &w = b->wit_cover[i >> 6];
+        const uint64_t bit = 1ull << (i & 63);
+        if (!(w & bit)) b->wit_missing--;
+        w |= bit;
+    }
+    return CW_OK;
+}
+// a HOST image: staged through d_bulk in pieces of piece_rows rows, synchronised before the staging buffer is written again
+// and before returning (the caller may free the image then), as cw_set_inputs_n8 does
+static int supply_host(cw_batch *b, uint32_t first, uint32_t count, const uint8_t *img, uint32_t eb) {
+    const size_t row = (size_t)b->c->n_witness * eb;
+    const uint32_t per = piece_rows(row, count);
+    if (count) HIPCHK(b->d_bulk.grow((size_t)per * row));
+    for (uint32_t done = 0; done < count; done += per) {
+        const uint32_t n = std::min(per, count - done);
+        HIPCHK(hipMemcpyAsync(b->d_bulk, img + (size_t)done * row, (size_t)n * row, hipMemcpyHostToDevice, b->stream));
+        if (int rc = supply_device(b, first + done, n, b->d_bulk, eb)) return rc;
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return CW_OK;
+}
+extern "C" int cw_set_witnesses(cw_batch *b, uint32_t first, uint32_t count, const uint8_t *le32) {
+    if (int rc = supply_ready(b, first, count, le32, 1)) return rc;
+    return supply_host(b, first, count, le32, 32);
+}
+extern "C" int cw_set_witnesses_n8(cw_batch *b, uint32_t first, uint32_t count, const void *le8) {
+    if (int rc = supply_ready(b, first, count, le8, 1)) return rc;
+    return supply_host(b, first, count, (const uint8_t *)le8, 8);
+}
+extern "C" int cw_set_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, const void *d_le32) {
+    if (int rc = supply_ready(b, first, count, d_le32, 16)) return rc;
+    return supply_device(b, first, count, d_le32, 32);
+}
+extern "C" int cw_set_witnesses_device_n8(cw_batch *b, uint32_t first, uint32_t count, const void *d_le8) {
+    if (int rc = supply_ready(b, first, count, d_le8, b && b->c->is64 ? 8 : 16)) return rc;
+    return supply_device(b, first, count, d_le8, 8);
+}
+extern "C" int64_t cw_witnesses_missing(const cw_batch *b) { return b && b->supplied ? (int64_t)b->wit_missing : -1; }
+
+// .wtns files in: every file through cw_wtns_parse (cw_wtns_read.h: the circuit's n8, prime and witness length, or CW_EIO with
+// the path and the reason), the bodies collected in a host staging image, one launch per piece - not one per file
+static int read_wtns_files(cw_batch *b, uint32_t first, uint32_t count, const char *pattern, bool is_pattern) {
+    const cw_circuit *c = b->c;
+    const uint32_t n8 = cw_element_bytes(c);
+    const size_t row = (size_t)c->n_witness * n8;
+    const uint32_t per = piece_rows(row, count);
+    std::vector<uint8_t> img((size_t)per * row), file;
+    for (uint32_t done = 0; done < count; done += per) {
+        const uint32_t n = std::min(per, count - done);
+        for (uint32_t k = 0; k < n; k++) {
+            char path[4096];
+            if (is_pattern) snprintf(path, sizeof path, pattern, first + done + k);
+            else snprintf(path, sizeof path, "%s", pattern);
+            if (!read_file(path, file)) return fail(CW_EIO, std::string("cannot read: ") + path);
+            const uint8_t *body = nullptr;
+            if (const char *why = cw_wtns_parse(file.data(), file.size(), n8, (const uint8_t *)c->q.w, c->n_witness, &body))
+                return fail(CW_EIO, std::string(path) + ": " + why);
+            memcpy(&img[(size_t)k * row], body, row);
+        }
+        NEED_DEVICE(b);
+        HIPCHK(hipSetDevice(b->device));
+        if (int rc = supply_host(b, first + done, n, img.data(), n8)) return rc;
+    }
+    return CW_OK;
+}
+extern "C" int cw_read_wtns(cw_batch *b, uint32_t instance, const char *path) {
+    if (int rc = supply_args(b, instance, 1, path, 1)) return rc;
+    return read_wtns_files(b, instance, 1, path, false);
+}
+// `pattern`: a printf pattern with exactly one %u / %d (the instance number), as cw_write_wtns_many takes it
+extern "C" int cw_read_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern) {
+    if (!b || !pattern) return fail(CW_EINVAL, "null argument");
+    if (int rc = check_file_pattern(pattern)) return rc;
+    if (int rc = supply_args(b, first, count, pattern, 1)) return rc;
+    return read_wtns_files(b, first, count, pattern, true);
 }
 
 // Debug trace of one instance (the reference prints template, line and the component trace of a failed `===` and
@@ -3511,6 +3639,7 @@ extern "C" int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, 
     if (s == 0) t += "ok\n";
     if (s & CW_ST_ASSERT_FAILED) t += "a run-time check (=== / assert) failed: operation " + std::to_string(s >> 8) + " of the witness program (the first failing one in program order)\n";
     if (s & CW_ST_ARITH) t += "integer division or modulo by zero (or a run-away function): operation " + std::to_string(s >> 8) + " of the witness program\n";
+    if (s & CW_ST_BAD_WITNESS) t += "the supplied witness is malformed: a value that is not a canonical residue, or an entry 0 that is not 1\n";
     if (s & CW_ST_R1CS_FAILED) {
         const uint32_t k = fb[instance];
         t += "constraint " + std::to_string(k) + " of the .r1cs is violated: A*B - C != 0 with\n";
@@ -3576,6 +3705,9 @@ extern "C" int64_t cw_get_log(cw_batch *b, uint32_t instance, char *out, size_t 
     if (!b || (!out && out_len)) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch) return fail(CW_EINVAL, "instance out of range");
     cw_circuit *c = b->c;
+    if (b->supplied)
+        return fail(CW_ESTATE, "cw_get_log: no witness program has run on this table (the witnesses were supplied): the hidden log "
+                               "values were never written");
     std::string t;
     if (!c->logs.empty()) {
         // circuits with log statements never run as bit-plane batches (compiler.lower_bitplane), so the status word of ONE

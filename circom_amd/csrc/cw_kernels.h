@@ -76,3 +76,8 @@ hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint3
 // bulk egress as a tiled transpose: [count][n_wit][elem_bytes], elem_bytes = 8 or 32 (32: `out` 16-byte aligned)
 hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
                         void *out, uint32_t elem_bytes);
+// supplied witnesses, the same transpose the other way: [count][n_wit][elem_bytes] -> V[w2s[k]][first + j], entry 0 excepted;
+// CW_ST_BAD_WITNESS into status[first + j] for a value that is not canonical or an entry 0 that is not 1 (8: `in` 8-byte aligned,
+// 32: 16-byte aligned)
+hipError_t cwk64_wit_ingest(hipStream_t s, const void *in, void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
+                            uint32_t count, uint32_t *status, uint32_t elem_bytes);

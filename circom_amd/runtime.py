@@ -16,7 +16,7 @@ import numpy as np
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["CW_LIB"]).resolve() if os.environ.get("CW_LIB") else _HERE / "lib" / "libcircom_amd.so"   # CW_LIB: diagnostics builds
 
-ST_OK, ST_ASSERT_FAILED, ST_ARITH, ST_R1CS_FAILED = 0, 1, 2, 4
+ST_OK, ST_ASSERT_FAILED, ST_ARITH, ST_R1CS_FAILED, ST_BAD_WITNESS = 0, 1, 2, 4, 8
 
 
 class CwError(RuntimeError):
@@ -31,7 +31,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_fn64.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -110,6 +110,13 @@ _SIGS = {
     "cw_get_r1cs_first_bad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_write_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtnsb": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cw_set_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_set_witnesses_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_set_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_set_witnesses_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_read_wtns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
+    "cw_read_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
+    "cw_witnesses_missing": (C.c_int64, [C.c_void_p]),
     "cw_explain": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_size_t]),
     "cw_n_log_statements": (C.c_uint32, [C.c_void_p]),
     "cw_get_log": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]),
@@ -323,6 +330,41 @@ class Batch:
 
     def remaining_inputs(self, instance: int) -> int:
         return lib().cw_remaining_inputs(self.h, instance)
+
+    # -- witnesses in (64-bit runtime: check witnesses this batch did not compute) ------------------------
+    def set_witnesses(self, rows, first: int = 0):
+        """supply witnesses for the instances first .. first + len(rows): lists of ints or an array [count][n_witness] in
+        witness-list order (cw_set_witnesses_n8 when the circuit's element is 8 bytes - values must be below 2^64 -, else
+        cw_set_witnesses).  Values that are not canonical are stored reduced and flagged ST_BAD_WITNESS."""
+        nw = self.circuit.n_witness
+        if self.circuit.element_bytes == 8:
+            arr = np.ascontiguousarray(np.asarray(rows, dtype=np.uint64), dtype="<u8").reshape(-1, nw)
+            _chk(lib().cw_set_witnesses_n8(self.h, first, arr.shape[0], arr.ctypes.data_as(C.c_void_p)))
+            return
+        if not isinstance(rows, np.ndarray):
+            rows = np.frombuffer(b"".join(fe_to_bytes(row) for row in rows), dtype=np.uint8)
+        arr = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert arr.size % (nw * 32) == 0, "witness array has the wrong size"
+        _chk(lib().cw_set_witnesses(self.h, first, arr.size // (nw * 32), arr.ctypes.data_as(C.c_void_p)))
+
+    def set_witnesses_device(self, first: int, count: int, dptr: int):
+        """device image [count][n_witness][32], 16-byte aligned, read in stream order inside the call (cw_set_witnesses_device)"""
+        _chk(lib().cw_set_witnesses_device(self.h, first, count, C.c_void_p(dptr)))
+
+    def set_witnesses_device_n8(self, first: int, count: int, dptr: int):
+        """device image [count][n_witness][8], 8-byte aligned (cw_set_witnesses_device_n8)"""
+        _chk(lib().cw_set_witnesses_device_n8(self.h, first, count, C.c_void_p(dptr)))
+
+    def read_wtns(self, instance: int, path):
+        _chk(lib().cw_read_wtns(self.h, instance, os.fsencode(str(path))))
+
+    def read_wtns_many(self, first: int, count: int, pattern):
+        """`pattern`: one %u / %d = the instance number, as write_wtns_many"""
+        _chk(lib().cw_read_wtns_many(self.h, first, count, os.fsencode(str(pattern))))
+
+    def witnesses_missing(self) -> int:
+        """instances not supplied yet; -1 when the batch is not in the supplied state"""
+        return lib().cw_witnesses_missing(self.h)
 
     # -- compute ------------------------------------------------------------------------------------
     def run(self):

@@ -43,6 +43,8 @@ typedef struct cw_batch cw_batch;     /* replaces Circom_CalcWit (calcwit.hpp:17
    several checks of an instance fail, the one with the smallest index is reported whatever the schedule's row order and
    strand count - the check the reference's sequential program stops at (assert_bucket.rs:75-77, calcwit.cpp:104-114). */
 #define CW_ST_R1CS_FAILED 4u   /* set by cw_check_r1cs */
+#define CW_ST_BAD_WITNESS 8u   /* a SUPPLIED witness (cw_set_witnesses*, cw_read_wtns*) was malformed: a value that is not a canonical
+                                  residue, or an entry 0 that is not 1.  Bits 4..7 are unused. */
 
 const char *cw_last_error(void);
 const char *cw_version(void);
@@ -244,6 +246,48 @@ int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *
  * re-ran) for bit-plane batches.  Format: csrc/cw_host.cpp at cw_write_wtnsb; reader / expander circom_amd/wtnsb.py
  * (`expand(i)` = the bytes cw_write_wtns writes for instance i, main.cpp:288-334). */
 int cw_write_wtnsb(cw_batch *b, const char *path);
+/* ---- witnesses IN: check witnesses this batch did not compute (64-bit runtime) ------------------------------------------
+ * The `.wtns` files of another calculator (the reference runtime, an older build, another machine), or an image streamed out
+ * earlier with cw_get_witnesses_device(_n8), go back into the value table, and cw_check_r1cs, cw_explain and every egress work
+ * on them - the batch counterpart of `snarkjs wtns check`.  The image is [count][n_witness][element] little-endian in the order
+ * of the circuit's witness list (cw_set_witness_list), element = 32 bytes (cw_set_witnesses, _device) or cw_element_bytes = 8
+ * (the _n8 forms, the files); instance j of the image is instance first + j of the batch.  One tiled transpose on the device
+ * (csrc/cw64.hip cw64_wit_ingest_kernel), the mirror image of the bulk egress.
+ *   validation  nothing is repaired quietly.  The value stored is the reduced one (the check needs a residue), and
+ *               CW_ST_BAD_WITNESS is set in the instance's status word when a value was not canonical (>= p; in the 32-byte
+ *               form also: any of the upper three words set) or entry 0 is not 1.  Entry 0 is not stored: the constant wire
+ *               stays 1, so the constant terms of the check stay meaningful for the other wires.
+ *   state       the FIRST supply since cw_batch_create or since the last cw_run clears every status word and first-bad row and
+ *               the coverage record; the batch is then "supplied".  Later supplies add coverage.  An instance supplied twice is
+ *               overwritten; a CW_ST_BAD_WITNESS bit (or a CW_ST_R1CS_FAILED bit of an earlier check) it had stays set until
+ *               the next cw_run or the next first supply.  cw_witnesses_missing: instances not covered yet, -1 when the batch
+ *               is not in the supplied state.  cw_check_r1cs answers CW_ESTATE "witnesses missing for N instances" until that
+ *               is 0; run twice on the same table it gives the same words.  cw_run ends the supplied state, and so does
+ *               cw_run_check: plain or replayed from its graph it begins with the table's init and the ingest of the INPUTS, so
+ *               it computes the batch's own witnesses over whatever was supplied.
+ *   served      cw_get_status, cw_get_r1cs_first_bad, cw_explain, cw_get_witness(es)(_device)(_n8), cw_stream_witnesses_device,
+ *               cw_get_public(_device), cw_write_wtns(_many), cw_write_wtnsb read the table through the witness list and work
+ *               unchanged.  No witness program has run on a supplied table: cw_get_signal of a signal the witness list does not
+ *               name and cw_get_log answer CW_ESTATE (temporaries and hidden log values were never written).  With a shortened
+ *               witness list the check is meaningful when the .r1cs names listed signals only.
+ *   lifetime    the host forms and the file forms copy in pieces and synchronise before they return.  The device forms launch
+ *               the kernel inside the call: the buffer is read in stream order and may be reused once the batch's stream has
+ *               passed the call - nothing is deferred to a later call, unlike cw_set_inputs_device.
+ *   alignment   d_le8: 8 bytes, d_le32: 16 bytes, CW_EINVAL otherwise (the pointer is not touched).
+ *   files       cw_read_wtns / cw_read_wtns_many (`pattern`: one %u / %d = the instance number, as cw_write_wtns_many) check
+ *               magic, version, the two sections in either order, n8 = cw_element_bytes, the circuit's prime, nWitness =
+ *               cw_n_witness, a body of exactly nWitness x n8 bytes and nothing behind it (csrc/cw_wtns_read.h); each refusal
+ *               is CW_EIO with the path and the reason.  Many files go to the device as one image per 256 MiB.
+ *   engines     circuits of the 256-bit schedule and bit-plane circuits answer CW_ESTATE "supplied witnesses are served by the
+ *               64-bit runtime only (--prime goldilocks)".
+ * Every call checks in this order: null / range / alignment (CW_EINVAL), engine (CW_ESTATE), [the files (CW_EIO)], device. */
+int cw_set_witnesses(cw_batch *b, uint32_t first, uint32_t count, const uint8_t *le32);
+int cw_set_witnesses_n8(cw_batch *b, uint32_t first, uint32_t count, const void *le8);
+int cw_set_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, const void *d_le32);
+int cw_set_witnesses_device_n8(cw_batch *b, uint32_t first, uint32_t count, const void *d_le8);
+int cw_read_wtns(cw_batch *b, uint32_t instance, const char *path);
+int cw_read_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern);
+int64_t cw_witnesses_missing(const cw_batch *b);
 /* human-readable trace of one instance into out[out_len]: decoded status word and, for a violated constraint, its index
  * and every wire with its name from <name>.sym (may be NULL) and value — the batch counterpart of the trace the
  * reference prints before aborting (c_code_generator.rs:461-468, calcwit.cpp:104-114) */
