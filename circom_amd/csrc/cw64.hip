@@ -13,6 +13,7 @@
 //   any q (tests/golden/reference_wtns_goldilocks.json: vectors from the reference's own 64-bit runtime, incl. the operator zoo)
 #include <hip/hip_runtime.h>
 #include "cw_kernels.h"
+#include "cw_pieces.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
 #define GL_HALF (GL_P >> 1)
@@ -74,7 +75,7 @@ __global__ void __launch_bounds__(256) cw64_init_kernel(uint64_t *V, uint32_t Bp
 // inputs arrive as [batch][n_in][EB] little-endian values: EB = 32, the boundary's element, or EB = 8, the element of this
 // runtime; a value that is not a canonical residue (upper words set, or >= p) is reduced, as Fr_str2element does for what
 // loadJson reads.  Lane = instance, blockIdx.y = input: consecutive lanes read values n_in * EB bytes apart.  This is the
-// kernel for narrow circuits and for a 32-byte image at an address that is no multiple of 16 (cw64_ingest_tiled_kernel below).
+// kernel for narrow circuits and for a 32-byte image at an address that is no multiple of 16 (cw64_transpose_in_kernel below).
 template <int EB>
 __global__ void __launch_bounds__(256) cw64_ingest_kernel(const uint64_t *__restrict__ in, uint64_t *V, uint32_t input_start, uint32_t n_in,
                                                           uint32_t batch, uint32_t Bp) {
@@ -378,19 +379,24 @@ __global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__rest
     }
 }
 
-// Bulk ingest as the same transpose in the other direction: [batch][n_in][EB] bytes, EB = 32 (the boundary's element) or 8 (this
-// runtime's), into V[input_start + k][instance].  cw64_ingest_kernel gives consecutive lanes consecutive INSTANCES: every lane
-// reads another row of the image, n_in * EB bytes from its neighbour's - 64 cache lines for 512 useful bytes, and each of those
-// lines is asked for again by the workgroups of up to n_in other inputs.  Here a workgroup of four waves owns 64 instances x
-// EG_T inputs, and no other workgroup requests a byte of its part of the image:
+// The transpose INTO the value table, the egress transpose in the other direction, in two uses:
+//   bulk ingest (WIT = false): [count][n][EB] bytes of inputs, EB = 32 (the boundary's element) or 8 (this runtime's), input k of
+//           instance j into V[slot0 + k][first + j];
+//   supplied witnesses (WIT = true; cw_set_witnesses*, cw_read_wtns*): [count][n][EB] bytes of witnesses, EB = 8 (this runtime's
+//           .wtns element) or 32, entry k of instance j into V[w2s[k]][first + j] - the mirror image of cw64_egress_kernel.
+// cw64_ingest_kernel gives consecutive lanes consecutive INSTANCES: every lane reads another row of the image, n * EB bytes from
+// its neighbour's - 64 cache lines for 512 useful bytes, and each of those lines is asked for again by the workgroups of up to
+// n other inputs.  Here a workgroup of four waves owns 64 instances x EG_T entries, and no other workgroup requests a byte of
+// its part of the image:
 //   read    wave w takes the instances j = w, w + 4, ... of the tile; consecutive lanes read consecutive pieces of the row
-//           in[j0 + j][k0 .. k0 + EG_T): 8-byte form: the 64 values, 512 contiguous bytes (8-byte loads: with n_in odd a row
+//           in[j0 + j][k0 .. k0 + EG_T): 8-byte form: the 64 values, 512 contiguous bytes (8-byte loads: with n odd a row
 //           starts on an 8-byte boundary only); 32-byte form: 16-byte pieces, lane l holds words {0, 1} (l even) or {2, 3} (l odd)
-//           of value l / 2 (+ 32 in the second load), 1 KiB contiguous per load, two loads per row.  `in` must be 16-byte
-//           aligned in the 32-byte form.  The 16 (32) loads of a wave are issued before the first value is used.
+//           of value l / 2 (+ 32 in the second load), 1 KiB contiguous per load, two loads per row.  `in` must be 8-byte aligned
+//           in the 8-byte form and 16-byte aligned in the 32-byte form.  The 16 (32) loads of a wave are issued before the first
+//           value is used.
 //   reduce  8-byte form: one conditional subtraction of p.  32-byte form: w0 + w1 e + w2 e^2 + w3 e^3 with e = 2^32 - 1 = 2^64
 //           (mod p), every word brought below p first.  The even lane forms w0 + w1 e, the odd lane (w2 + w3 e) e^2, and one
-//           exchange between neighbours adds the two.  Nearly every real input has words 1..3 zero: a ballot over the wave
+//           exchange between neighbours adds the two.  Nearly every real value has words 1..3 zero: a ballot over the wave
 //           (even lanes: w1, odd lanes: w2 | w3) skips multiplications and exchange for the whole load - the branch is
 //           wave-uniform, and a wave pays for the long form only for the loads that hold such a value.
 //   stage   tile[k][j] in LDS with rows of EG_S = 65 words of 8 bytes, the egress kernel's tile written and read the other way
@@ -402,138 +408,68 @@ __global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__rest
 //           every bank once, whatever the row's start.
 //           (This is arithmetic from the documented bank rules, as the egress comment is: nobody has taken a bank-conflict
 //           counter pass on either kernel.)
-//   write   wave w takes the inputs k = w, w + 4, ...; its 64 lanes store 64 consecutive instances of V[input_start + k0 + k]:
-//           one 512-byte store, as the evaluation kernel writes its results.
-// Lanes past `batch` and inputs past n_in neither read nor write; nothing is read past the end of the image.
-template <int EB>
-__global__ void __launch_bounds__(256) cw64_ingest_tiled_kernel(const uint8_t *__restrict__ in, uint64_t *__restrict__ V, uint32_t input_start,
-                                                                uint32_t n_in, uint32_t batch, uint32_t Bp) {
-    __shared__ uint64_t tile[EG_T * EG_S];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
-    const uint32_t nk = n_in - k0 < EG_T ? n_in - k0 : EG_T, nj = batch - j0 < 64u ? batch - j0 : 64u;
-    // The loads of a wave stand in ONE block of straight-line code under the lane's own condition, the same for all of them (the
-    // row bases are wave-uniform: scalar registers, the lane is the offset).  A condition per load would make every load a branch
-    // of its own that waits for its data before the next one is issued.  The last instance tile of a batch (nj < 64) has a row
-    // condition too and takes that slower form.
-    if (EB == 8) {
-        const uint64_t *t0 = (const uint64_t *)in + (size_t)j0 * n_in + k0;
-        uint64_t v[64 / 4] = {};
-        if (lane < nk) {
-            if (nj == 64u) {
-#pragma unroll
-                for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * n_in + lane];
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 64 / 4; i++)
-                    if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * n_in + lane];
-            }
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < 64 / 4; i++) tile[lane * EG_S + wave + 4 * i] = gl_wrap(v[i]);
-    } else {
-        const uint4 *t0 = (const uint4 *)in + ((size_t)j0 * n_in + k0) * 2;
-        const bool odd = lane & 1u;
-        uint4 v[64 / 4][2] = {};
-        if (nj == 64u && nk == EG_T) {                                 // a full tile: all 32 loads of the wave in one block
-#pragma unroll
-            for (uint32_t i = 0; i < 64 / 4; i++) {
-                v[i][0] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane];
-                v[i][1] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64];
-            }
-        } else
-#pragma unroll
-        for (uint32_t h = 0; h < 2; h++) {
-            if (((lane + 64 * h) >> 1) < nk) {
-                if (nj == 64u) {
-#pragma unroll
-                    for (uint32_t i = 0; i < 64 / 4; i++) v[i][h] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64 * h];
-                } else {
-#pragma unroll
-                    for (uint32_t i = 0; i < 64 / 4; i++)
-                        if (wave + 4 * i < nj) v[i][h] = t0[(size_t)(wave + 4 * i) * n_in * 2 + lane + 64 * h];
-                }
-            }
-        }
-        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2 (mod p)
-        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e);
-#pragma unroll
-        for (uint32_t i = 0; i < 64 / 4; i++) {
-#pragma unroll
-            for (uint32_t h = 0; h < 2; h++) {
-                const uint64_t lo = ((uint64_t)v[i][h].y << 32) | v[i][h].x, hi = ((uint64_t)v[i][h].w << 32) | v[i][h].z;
-                uint64_t r = gl_wrap(lo);
-                if (__builtin_amdgcn_ballot_w64(odd ? (lo | hi) != 0 : hi != 0)) {
-                    uint64_t part = gl_add(r, gl_mul(gl_wrap(hi), e));
-                    if (odd) part = gl_mul(part, e2);
-                    r = gl_add(part, (uint64_t)__shfl_xor((unsigned long long)part, 1));
-                }
-                if (!odd) tile[((lane >> 1) + 32 * h) * EG_S + wave + 4 * i] = r;
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t k = wave; k < nk; k += 4)
-        if (lane < nj) V[(size_t)(input_start + k0 + k) * Bp + j0 + lane] = tile[k * EG_S + lane];
-}
-
-// Supplied witnesses (cw_set_witnesses*, cw_read_wtns*): the mirror image of cw64_egress_kernel.  [count][n_wit][EB] bytes, EB = 8
-// (this runtime's .wtns element) or 32 (the boundary's), entry k of instance j into V[w2s[k]][first + j].  The transpose is the
-// one of cw64_ingest_tiled_kernel above - same work distribution (a workgroup of four waves owns 64 instances x EG_T entries),
-// same loads in one straight-line block, same reduction, the same 65-word tile written column-wise and read row-wise, so the
-// bank arithmetic of the comment above that kernel holds here word for word - with two differences:
-//   write   the slot of entry k0 + k is w2s[k0 + k], not input_start + k0 + k: wave-uniform, a scalar load with the index
-//           clamped to the list as the egress kernel clamps it, the 16 loads of a wave ahead of its 16 stores of 512 bytes.
-//           Entry 0 is NOT stored: slot 0 keeps the 1 of cw64_init_kernel, so that the constant terms of the R1CS check stay
-//           meaningful for the other wires of a witness whose entry 0 is wrong.
+//   write   wave w takes the entries k = w, w + 4, ...; its 64 lanes store 64 consecutive instances of the entry's slot: one
+//           512-byte store, as the evaluation kernel writes its results.  `first` need not be a multiple of 64: a row of V is
+//           8-byte aligned wherever it starts.
+// Lanes past `count` and entries past n neither read nor write; nothing is read past the end of the image.
+// The supplied-witness use differs in the slot and in a check, and in nothing else:
+//   write   the slot of entry k0 + k is w2s[k0 + k], not slot0 + k0 + k: wave-uniform, a scalar load with the index clamped to
+//           the list as the egress kernel clamps it, the 16 loads of a wave ahead of its 16 stores.  Entry 0 is NOT stored:
+//           slot 0 keeps the 1 of cw64_init_kernel, so that the constant terms of the R1CS check stay meaningful for the other
+//           wires of a witness whose entry 0 is wrong.
 //   check   a checker must not quietly repair what it is given.  The reduced value is stored (the check cannot run without
 //           one), and CW_ST_BAD_WITNESS is or'ed into status[first + j] when a value of instance j was not canonical (8-byte
 //           form: >= p; 32-byte form: word 0 >= p or any of words 1..3 set) or its entry 0 is not 1.  On the read side a WAVE
 //           holds one instance's row of the tile per load: one ballot per load (the 32-byte form's is the ballot that skips the
 //           long reduction) sets bit i of a wave-uniform mask, i = the wave's i-th instance, and lane i issues the atomicOr -
 //           at most 16 per wave, none for well-formed witnesses.  Another workgroup may report the same instance for another
-//           entry tile: or is idempotent.
-// Lanes past `count` and entries past n_wit neither read nor write (their registers stay 0, which no test above flags - the
-// entry-0 test is under the row's own condition); nothing is read past the end of the image.  `first` need not be a multiple
-// of 64: a row of V is 8-byte aligned wherever it starts.  `in`: 8-byte aligned (EB = 8), 16-byte aligned (EB = 32).
-template <int EB>
-__global__ void __launch_bounds__(256) cw64_wit_ingest_kernel(const uint8_t *__restrict__ in, uint64_t *__restrict__ V,
-                                                              const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
-                                                              uint32_t count, uint32_t *status) {
+//           entry tile: or is idempotent.  (The registers of lanes that read nothing stay 0, which no test flags - the entry-0
+//           test is under the row's own condition.)
+// The bulk ingest pays for none of it: no ballot for `bad`, no atomicOr, no load from w2s (w2s and status are null there).
+template <int EB, bool WIT>
+__global__ void __launch_bounds__(256) cw64_transpose_in_kernel(const uint8_t *__restrict__ in, uint64_t *__restrict__ V,
+                                                                const uint32_t *__restrict__ w2s, uint32_t slot0, uint32_t n, uint32_t Bp,
+                                                                uint32_t first, uint32_t count, uint32_t *status) {
     __shared__ uint64_t tile[EG_T * EG_S];
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
-    const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
-    const bool entry0 = k0 == 0 && lane == 0;                          // this lane's (first) piece is the head of entry 0
+    const uint32_t nk = n - k0 < EG_T ? n - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool entry0 = WIT && k0 == 0 && lane == 0;                   // this lane's (first) piece is the head of entry 0
     uint32_t badmask = 0;                                              // bit i: instance wave + 4 i of the tile is malformed (wave-uniform)
+    // The loads of a wave stand in ONE block of straight-line code under the lane's own condition, the same for all of them (the
+    // row bases are wave-uniform: scalar registers, the lane is the offset).  A condition per load would make every load a branch
+    // of its own that waits for its data before the next one is issued.  The last instance tile of a batch (nj < 64) has a row
+    // condition too and takes that slower form.
     if (EB == 8) {
-        const uint64_t *t0 = (const uint64_t *)in + (size_t)j0 * n_wit + k0;
+        const uint64_t *t0 = (const uint64_t *)in + (size_t)j0 * n + k0;
         uint64_t v[64 / 4] = {};
         if (lane < nk) {
             if (nj == 64u) {
 #pragma unroll
-                for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * n_wit + lane];
+                for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * n + lane];
             } else {
 #pragma unroll
                 for (uint32_t i = 0; i < 64 / 4; i++)
-                    if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * n_wit + lane];
+                    if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * n + lane];
             }
         }
 #pragma unroll
         for (uint32_t i = 0; i < 64 / 4; i++) {
-            const bool bad = v[i] >= GL_P || (entry0 && wave + 4 * i < nj && v[i] != 1);
-            if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+            if (WIT) {
+                const bool bad = v[i] >= GL_P || (entry0 && wave + 4 * i < nj && v[i] != 1);
+                if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+            }
             tile[lane * EG_S + wave + 4 * i] = gl_wrap(v[i]);
         }
     } else {
-        const uint4 *t0 = (const uint4 *)in + ((size_t)j0 * n_wit + k0) * 2;
+        const uint4 *t0 = (const uint4 *)in + ((size_t)j0 * n + k0) * 2;
         const bool odd = lane & 1u;
         uint4 v[64 / 4][2] = {};
         if (nj == 64u && nk == EG_T) {                                 // a full tile: all 32 loads of the wave in one block
 #pragma unroll
             for (uint32_t i = 0; i < 64 / 4; i++) {
-                v[i][0] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane];
-                v[i][1] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64];
+                v[i][0] = t0[(size_t)(wave + 4 * i) * n * 2 + lane];
+                v[i][1] = t0[(size_t)(wave + 4 * i) * n * 2 + lane + 64];
             }
         } else
 #pragma unroll
@@ -541,11 +477,11 @@ __global__ void __launch_bounds__(256) cw64_wit_ingest_kernel(const uint8_t *__r
             if (((lane + 64 * h) >> 1) < nk) {
                 if (nj == 64u) {
 #pragma unroll
-                    for (uint32_t i = 0; i < 64 / 4; i++) v[i][h] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64 * h];
+                    for (uint32_t i = 0; i < 64 / 4; i++) v[i][h] = t0[(size_t)(wave + 4 * i) * n * 2 + lane + 64 * h];
                 } else {
 #pragma unroll
                     for (uint32_t i = 0; i < 64 / 4; i++)
-                        if (wave + 4 * i < nj) v[i][h] = t0[(size_t)(wave + 4 * i) * n_wit * 2 + lane + 64 * h];
+                        if (wave + 4 * i < nj) v[i][h] = t0[(size_t)(wave + 4 * i) * n * 2 + lane + 64 * h];
                 }
             }
         }
@@ -557,31 +493,43 @@ __global__ void __launch_bounds__(256) cw64_wit_ingest_kernel(const uint8_t *__r
             for (uint32_t h = 0; h < 2; h++) {
                 const uint64_t lo = ((uint64_t)v[i][h].y << 32) | v[i][h].x, hi = ((uint64_t)v[i][h].w << 32) | v[i][h].z;
                 uint64_t r = gl_wrap(lo);
-                if (__builtin_amdgcn_ballot_w64(odd ? (lo | hi) != 0 : hi != 0)) {         // words 1..3 set: malformed, and the long form
-                    badmask |= 1u << i;
+                if (__builtin_amdgcn_ballot_w64(odd ? (lo | hi) != 0 : hi != 0)) {         // words 1..3 set: the long form (WIT: malformed)
+                    if (WIT) badmask |= 1u << i;
                     uint64_t part = gl_add(r, gl_mul(gl_wrap(hi), e));
                     if (odd) part = gl_mul(part, e2);
                     r = gl_add(part, (uint64_t)__shfl_xor((unsigned long long)part, 1));
                 }
-                const bool bad = !odd && (lo >= GL_P || (h == 0 && entry0 && wave + 4 * i < nj && lo != 1));
-                if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+                if (WIT) {
+                    const bool bad = !odd && (lo >= GL_P || (h == 0 && entry0 && wave + 4 * i < nj && lo != 1));
+                    if (__builtin_amdgcn_ballot_w64(bad)) badmask |= 1u << i;
+                }
                 if (!odd) tile[((lane >> 1) + 32 * h) * EG_S + wave + 4 * i] = r;
             }
         }
     }
-    if (lane < 64 / 4 && ((badmask >> lane) & 1u)) atomicOr(&status[first + j0 + wave + 4 * lane], CW_ST_BAD_WITNESS);
+    if (WIT && lane < 64 / 4 && ((badmask >> lane) & 1u)) atomicOr(&status[first + j0 + wave + 4 * lane], CW_ST_BAD_WITNESS);
     __syncthreads();
-    uint64_t *Vj = V + first + j0 + lane;
-    uint32_t slot[EG_T / 4];
+    // The write is where the slot differs, and each use keeps its own loop.  The witness list's: unrolled, the 16 scalar loads
+    // ahead of the stores, through the lane's own pointer into the row.  The inputs': rolled, the instance added per store.
+    // (A 64-bit per-lane value that outlives the barrier costs the 8-byte bulk ingest 24 VGPRs, 42 -> 66: its zero-extended lane
+    // is computed above the load block, and the compiler then keeps the zeros of v[] for the lanes past nk and the loaded values
+    // in registers of their own, joined by copies, instead of loading over the zeros.)
+    if (WIT) {
+        uint64_t *Vj = V + first + j0 + lane;
+        uint32_t slot[EG_T / 4];
 #pragma unroll
-    for (uint32_t i = 0; i < EG_T / 4; i++) {
-        const uint32_t k = wave + 4 * i;
-        slot[i] = w2s[k < nk ? k0 + k : k0];                         // always an entry of the list: the scalar load needs no branch
-    }
+        for (uint32_t i = 0; i < EG_T / 4; i++) {
+            const uint32_t k = wave + 4 * i;
+            slot[i] = w2s[k < nk ? k0 + k : k0];                     // always an entry of the list: the scalar load needs no branch
+        }
 #pragma unroll
-    for (uint32_t i = 0; i < EG_T / 4; i++) {
-        const uint32_t k = wave + 4 * i;
-        if (k < nk && k0 + k != 0 && lane < nj) Vj[(size_t)slot[i] * Bp] = tile[k * EG_S + lane];
+        for (uint32_t i = 0; i < EG_T / 4; i++) {
+            const uint32_t k = wave + 4 * i;
+            if (k < nk && k0 + k != 0 && lane < nj) Vj[(size_t)slot[i] * Bp] = tile[k * EG_S + lane];
+        }
+    } else {
+        for (uint32_t k = wave; k < nk; k += 4)
+            if (lane < nj) V[(size_t)(slot0 + k0 + k) * Bp + first + j0 + lane] = tile[k * EG_S + lane];
     }
 }
 
@@ -603,47 +551,31 @@ hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_s
         hipLaunchKernelGGL(cw64_ingest_kernel<32>, grid, dim3(256), 0, s, (const uint64_t *)in, (uint64_t *)V, input_start, n_in, batch, Bp);
     return hipGetLastError();
 }
-// elem_bytes = 8 (`in` 8-byte aligned) or 32 (16-byte aligned); a launch holds at most 65 535 tiles of 64 instances (gridDim.y),
-// larger batches are split as cwk64_egress splits them; the input tiles are gridDim.x, so n_in is not limited
+// The launches of cw64_transpose_in_kernel: elem_bytes = 8 (`in` 8-byte aligned) or 32 (16-byte aligned); a launch holds at most
+// 65 535 tiles of 64 instances (gridDim.y), larger counts are split as cwk64_egress splits them, and nothing more is launched
+// behind a launch that failed; the entry tiles are gridDim.x, so n is not limited
+static hipError_t transpose_in(bool wit, hipStream_t s, const void *in, void *V, const uint32_t *w2s, uint32_t slot0, uint32_t n, uint32_t Bp,
+                               uint32_t first, uint32_t count, uint32_t *status, uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if ((uintptr_t)in & (elem_bytes == 32 ? 15 : 7)) return hipErrorInvalidValue;
+    if (!n || !count) return hipSuccess;
+    const auto kernel = wit ? (elem_bytes == 8 ? cw64_transpose_in_kernel<8, true> : cw64_transpose_in_kernel<32, true>)
+                            : (elem_bytes == 8 ? cw64_transpose_in_kernel<8, false> : cw64_transpose_in_kernel<32, false>);
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n + EG_T - 1) / EG_T, (m + 63) / 64), dim3(256), 0, s,
+                           (const uint8_t *)in + (size_t)done * n * elem_bytes, (uint64_t *)V, w2s, slot0, n, Bp, first + done, m, status);
+        return hipGetLastError();
+    });
+}
+// bulk inputs [batch][n_in][elem_bytes] into the slots from input_start, all columns of V
 hipError_t cwk64_ingest_tiled(hipStream_t s, const void *in, void *V, uint32_t input_start, uint32_t n_in, uint32_t batch, uint32_t Bp,
                               uint32_t elem_bytes) {
-    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
-    if ((uintptr_t)in & (elem_bytes == 32 ? 15 : 7)) return hipErrorInvalidValue;
-    if (!n_in || !batch) return hipSuccess;
-    const uint32_t per = 65535u * 64u;
-    for (uint32_t done = 0; done < batch; done += per) {
-        const uint32_t n = batch - done < per ? batch - done : per;
-        const dim3 grid((n_in + EG_T - 1) / EG_T, (n + 63) / 64);
-        const uint8_t *i = (const uint8_t *)in + (size_t)done * n_in * elem_bytes;
-        uint64_t *v = (uint64_t *)V + done;
-        if (elem_bytes == 8)
-            hipLaunchKernelGGL(cw64_ingest_tiled_kernel<8>, grid, dim3(256), 0, s, i, v, input_start, n_in, n, Bp);
-        else
-            hipLaunchKernelGGL(cw64_ingest_tiled_kernel<32>, grid, dim3(256), 0, s, i, v, input_start, n_in, n, Bp);
-        if (hipError_t e = hipGetLastError()) return e;              // nothing more is launched behind a launch that failed
-    }
-    return hipSuccess;
+    return transpose_in(false, s, in, V, nullptr, input_start, n_in, Bp, 0, batch, nullptr, elem_bytes);
 }
-// supplied witnesses [count][n_wit][elem_bytes] into the columns first .. first + count of V; elem_bytes = 8 (`in` 8-byte aligned)
-// or 32 (16-byte aligned); instance tiles split over launches of 65 535 as cwk64_egress splits them, and nothing more is
-// launched behind a launch that failed
+// supplied witnesses [count][n_wit][elem_bytes] into the columns first .. first + count of V
 hipError_t cwk64_wit_ingest(hipStream_t s, const void *in, void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
                             uint32_t count, uint32_t *status, uint32_t elem_bytes) {
-    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
-    if ((uintptr_t)in & (elem_bytes == 32 ? 15 : 7)) return hipErrorInvalidValue;
-    if (!n_wit || !count) return hipSuccess;
-    const uint32_t per = 65535u * 64u;
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = count - done < per ? count - done : per;
-        const dim3 grid((n_wit + EG_T - 1) / EG_T, (n + 63) / 64);
-        const uint8_t *i = (const uint8_t *)in + (size_t)done * n_wit * elem_bytes;
-        if (elem_bytes == 8)
-            hipLaunchKernelGGL(cw64_wit_ingest_kernel<8>, grid, dim3(256), 0, s, i, (uint64_t *)V, w2s, n_wit, Bp, first + done, n, status);
-        else
-            hipLaunchKernelGGL(cw64_wit_ingest_kernel<32>, grid, dim3(256), 0, s, i, (uint64_t *)V, w2s, n_wit, Bp, first + done, n, status);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return transpose_in(true, s, in, V, w2s, 0, n_wit, Bp, first, count, status, elem_bytes);
 }
 // calls: 0 = no O_CALL row in the program, 1 = register windows in the table, 2 = in LDS (lds_bytes = 512 x the registers of the
 // largest function, at most 64 KiB: what a launch gets as dynamic LDS without a function attribute)
@@ -666,31 +598,26 @@ hipError_t cwk64_r1cs(hipStream_t s, const void *chunks, uint32_t n_chunks, cons
                        n_chunks, (const uint4 *)terms, (const uint64_t *)V, Bp, batch, status, first_bad);
     return hipGetLastError();
 }
+// the instance is a grid dimension: launches of at most 65 535 instances, none behind one that failed
 hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
                         void *out) {
-    if (!n_wit || !count) return hipSuccess;
-    for (uint32_t done = 0; done < count; done += 65535u) {
-        const uint32_t n = count - done < 65535u ? count - done : 65535u;
+    if (!n_wit) return hipSuccess;
+    return cw_pieces(count, 65535u, [&](uint32_t done, uint32_t n) {
         hipLaunchKernelGGL(cw64_gather_kernel, dim3((n_wit + 255) / 256, n), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done,
                            n, (uint64_t *)out + (size_t)done * n_wit * 4);
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 // elem_bytes = 8 or 32; a launch holds at most 65 535 tiles of 64 instances (gridDim.y), larger counts are split as above
 hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
                         void *out, uint32_t elem_bytes) {
     if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
     if (elem_bytes == 32 && ((uintptr_t)out & 15)) return hipErrorInvalidValue;
-    if (!n_wit || !count) return hipSuccess;
-    const uint32_t per = 65535u * 64u;
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = count - done < per ? count - done : per;
-        const dim3 grid((n_wit + EG_T - 1) / EG_T, (n + 63) / 64);
-        uint8_t *o = (uint8_t *)out + (size_t)done * n_wit * elem_bytes;
-        if (elem_bytes == 8)
-            hipLaunchKernelGGL(cw64_egress_kernel<8>, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done, n, o);
-        else
-            hipLaunchKernelGGL(cw64_egress_kernel<32>, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, first + done, n, o);
-    }
-    return hipGetLastError();
+    if (!n_wit) return hipSuccess;
+    const auto kernel = elem_bytes == 8 ? cw64_egress_kernel<8> : cw64_egress_kernel<32>;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t n) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + EG_T - 1) / EG_T, (n + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp,
+                           first + done, n, (uint8_t *)out + (size_t)done * n_wit * elem_bytes);
+        return hipGetLastError();
+    });
 }

@@ -18,6 +18,7 @@
 // result is the reference's for every input.
 #include <hip/hip_runtime.h>
 #include "cw_kernels.h"
+#include "cw_pieces.h"
 #include "fp256.hip.h"
 
 
@@ -782,13 +783,13 @@ hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_
                            uint32_t count, void *out) {
     if (!count || !n_wit) return hipSuccess;
     const uint32_t kblocks = (n_wit + 128 * BITS_GATHER_RUN - 1) / (128 * BITS_GATHER_RUN);
-    for (uint32_t done = 0; done < count; done += 65535u * 64u) {       // grid.y limit
-        const uint32_t n = count - done < 65535u * 64u ? count - done : 65535u * 64u, groups = (n + 63) / 64;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t n) {   // grid.y limit; no launch behind one that failed
+        const uint32_t groups = (n + 63) / 64;
         const uint32_t gf = groups >= 8 && kblocks <= 65535u;           // see the kernel's comment
         hipLaunchKernelGGL(cw_bits_gather_kernel, gf ? dim3(groups, kblocks) : dim3(kblocks, groups), dim3(256), 0, s, (const uint64_t *)T, slots,
                            sh, wslot, n_wit, first + done, n, (uint4 *)out + (size_t)done * n_wit * 2, gf);
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                                   uint32_t batch) {
@@ -802,12 +803,11 @@ hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uin
 hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void *aos, const uint32_t *inst, uint32_t n_inst,
                                    uint32_t n_in, void *out) {
     if (!n_inst || !n_in) return hipSuccess;
-    for (uint32_t done = 0; done < n_inst; done += 65535u) {
-        const uint32_t n = n_inst - done < 65535u ? n_inst - done : 65535u;
+    return cw_pieces(n_inst, 65535u, [&](uint32_t done, uint32_t n) {
         hipLaunchKernelGGL(cw_bits_collect_inputs_kernel, dim3((n_in + 255) / 256, n), dim3(256), 0, s, (const uint64_t *)masks,
                            (const uint4 *)aos, inst + done, n, n_in, (uint4 *)out + (size_t)done * n_in * 2);
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,

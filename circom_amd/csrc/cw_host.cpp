@@ -21,6 +21,7 @@
 #include "cw_bits_host.h"
 #include "cw_devbuf.h"
 #include "cw_rerun.h"
+#include "cw_pieces.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
 
@@ -2603,7 +2604,7 @@ extern "C" int cw_set_inputs_json(cw_batch *b, uint32_t instance, const char *js
 // bit-plane mode
 // ---------------------------------------------------------------------------------------------------------
 // 64-bit runtime (cw64.hip): value table [slot][Bp] of uint64, the flat program, the R1CS terms
-// Input count from which cw_run ingests through cw64_ingest_tiled_kernel unless CW64_INGEST_TILED says otherwise.
+// Input count from which cw_run ingests through cw64_transpose_in_kernel unless CW64_INGEST_TILED says otherwise.
 // Measured, not guessed: tools/ubench_ingest64.py, profiles/ingest64_chain_65536.json, the table at the top of NOTES.md.  64 is the
 // smallest measured count (2, 16, 64, 1 024) at which the transpose is no slower than the kernel it replaces in BOTH element
 // widths; nothing was measured between 16 and 64.  ONE threshold for both widths on purpose: the 8-byte form already wins at 16
@@ -3227,13 +3228,12 @@ static int get_witnesses_host(cw_batch *b, uint32_t first, uint32_t count, uint8
     const size_t row = (size_t)c->n_witness * eb;
     const uint32_t per = std::max<uint32_t>(64, piece_rows(row, count) / 64 * 64);
     HIPCHK(b->d_bulk.grow((size_t)per * row));
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = std::min(per, count - done);
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t n) {
         if (int rc = device_egress(b, 0, c->n_witness, first + done, n, b->d_bulk, eb, true)) return rc;
         HIPCHK(hipMemcpyAsync(out + (size_t)done * row, b->d_bulk, (size_t)n * row, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
-    }
-    return CW_OK;
+        return CW_OK;
+    });
 }
 extern "C" int cw_get_witnesses(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) { return get_witnesses_host(b, first, count, out, 32); }
 extern "C" uint32_t cw_batch_call_lds(const cw_batch *b) { return b ? b->call_lds : 0; }
@@ -3264,16 +3264,12 @@ extern "C" int cw_stream_witnesses_device(cw_batch *b, uint32_t first, uint32_t 
                                           cw_chunk_fn consume, void *user) {
     if (!b || !d_buf0 || !d_buf1 || !consume || chunk == 0) return fail(CW_EINVAL, "null argument / zero chunk");
     if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "instance range out of the batch");
-    uint32_t n_chunk = 0;
-    for (uint32_t done = 0; done < count; done += chunk, n_chunk++) {
-        const uint32_t n = std::min(chunk, count - done);
-        void *buf = (n_chunk & 1) ? d_buf1 : d_buf0;
-        int rc = cw_get_witnesses_device(b, first + done, n, buf);
-        if (rc != CW_OK) return rc;
-        rc = consume(user, first + done, n, buf, (void *)b->stream);
-        if (rc != 0) return fail(CW_ESTATE, "the chunk consumer returned " + std::to_string(rc));
-    }
-    return CW_OK;
+    return cw_pieces(count, chunk, [&](uint32_t done, uint32_t n) {
+        void *buf = ((done / chunk) & 1) ? d_buf1 : d_buf0;
+        if (int rc = cw_get_witnesses_device(b, first + done, n, buf)) return rc;
+        const int rc = consume(user, first + done, n, buf, (void *)b->stream);
+        return rc ? fail(CW_ESTATE, "the chunk consumer returned " + std::to_string(rc)) : CW_OK;
+    });
 }
 
 // Public signals of every instance, [batch][n_public][32], written to DEVICE memory: what a multi-GPU job gathers to
@@ -3396,6 +3392,7 @@ extern "C" int cw_write_wtnsb(cw_batch *b, const char *path) {
     if (!b->bitmode) {
         const uint32_t per = piece_rows(row, batch);
         std::vector<uint8_t> buf((size_t)per * row);
+        // (not cw_pieces: a short write ends this walk too, and `ok` is no return value - the file is still to be closed)
         for (uint32_t done = 0; done < batch && rc == CW_OK && ok; done += per) {
             const uint32_t n = std::min(per, batch - done);
             rc = get_witnesses_host(b, done, n, buf.data(), n8);
@@ -3457,23 +3454,21 @@ extern "C" int cw_write_wtns_many(cw_batch *b, uint32_t first, uint32_t count, c
     const size_t row = (size_t)c->n_witness * eb;
     const uint32_t per = piece_rows(row, count);
     std::vector<uint8_t> buf((size_t)per * row);
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = std::min(per, count - done);
-        int rc = get_witnesses_host(b, first + done, n, buf.data(), eb);
-        if (rc) return rc;
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t n) {
+        if (int rc = get_witnesses_host(b, first + done, n, buf.data(), eb)) return rc;
         for (uint32_t k = 0; k < n; k++) {
             char path[4096];
             snprintf(path, sizeof path, pattern, first + done + k);
             if (int rc = write_wtns_file(c, path, buf.data() + (size_t)k * row)) return rc;
         }
-    }
-    return CW_OK;
+        return CW_OK;
+    });
 }
 
 // ---- supplied witnesses: witnesses IN (64-bit runtime) ----------------------------------------------------------------------
 // A batch becomes "has a table" a second way: the caller hands in witnesses computed elsewhere (another calculator's .wtns
 // files, an image streamed out earlier) and cw_check_r1cs / cw_explain / every egress work on them.  The image is
-// [count][n_witness][eb] in witness-list order and goes through cw64_wit_ingest_kernel (cw64.hip), the egress transpose the
+// [count][n_witness][eb] in witness-list order and goes through cw64_transpose_in_kernel<EB, true> (cw64.hip), the egress transpose the
 // other way, which also flags malformed witnesses (CW_ST_BAD_WITNESS).  State: the FIRST supply since creation or since the
 // last cw_run re-initialises status words, first-bad rows and slot 0 and clears the coverage record; later supplies only add
 // coverage (an instance supplied twice is overwritten and keeps a CW_ST_BAD_WITNESS bit it had); cw_run and cw_run_check start
@@ -3517,13 +3512,12 @@ static int supply_host(cw_batch *b, uint32_t first, uint32_t count, const uint8_
     const size_t row = (size_t)b->c->n_witness * eb;
     const uint32_t per = piece_rows(row, count);
     if (count) HIPCHK(b->d_bulk.grow((size_t)per * row));
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = std::min(per, count - done);
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t n) {
         HIPCHK(hipMemcpyAsync(b->d_bulk, img + (size_t)done * row, (size_t)n * row, hipMemcpyHostToDevice, b->stream));
         if (int rc = supply_device(b, first + done, n, b->d_bulk, eb)) return rc;
         HIPCHK(hipStreamSynchronize(b->stream));
-    }
-    return CW_OK;
+        return CW_OK;
+    });
 }
 extern "C" int cw_set_witnesses(cw_batch *b, uint32_t first, uint32_t count, const uint8_t *le32) {
     if (int rc = supply_ready(b, first, count, le32, 1)) return rc;
@@ -3551,8 +3545,7 @@ static int read_wtns_files(cw_batch *b, uint32_t first, uint32_t count, const ch
     const size_t row = (size_t)c->n_witness * n8;
     const uint32_t per = piece_rows(row, count);
     std::vector<uint8_t> img((size_t)per * row), file;
-    for (uint32_t done = 0; done < count; done += per) {
-        const uint32_t n = std::min(per, count - done);
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t n) {
         for (uint32_t k = 0; k < n; k++) {
             char path[4096];
             if (is_pattern) snprintf(path, sizeof path, pattern, first + done + k);
@@ -3565,9 +3558,8 @@ static int read_wtns_files(cw_batch *b, uint32_t first, uint32_t count, const ch
         }
         NEED_DEVICE(b);
         HIPCHK(hipSetDevice(b->device));
-        if (int rc = supply_host(b, first + done, n, img.data(), n8)) return rc;
-    }
-    return CW_OK;
+        return supply_host(b, first + done, n, img.data(), n8);
+    });
 }
 extern "C" int cw_read_wtns(cw_batch *b, uint32_t instance, const char *path) {
     if (int rc = supply_args(b, instance, 1, path, 1)) return rc;

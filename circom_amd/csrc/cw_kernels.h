@@ -58,6 +58,8 @@ hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, co
                          const FpParams &P);
 
 // ---- 64-bit runtime (cw64.hip: --prime goldilocks) ----
+// A call that needs several launches (cw_pieces.h: a grid dimension holds 65 535) checks every launch and launches nothing behind
+// one that failed; the bit-plane launchers above do the same.
 hipError_t cwk64_init(hipStream_t s, void *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad);
 // inputs [batch][n_in][elem_bytes], elem_bytes = 8 or 32: lane = instance (n_in <= 65 535) / a tiled transpose (8: `in` 8-byte
 // aligned, 32: 16-byte aligned; any n_in)
@@ -76,8 +78,8 @@ hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint3
 // bulk egress as a tiled transpose: [count][n_wit][elem_bytes], elem_bytes = 8 or 32 (32: `out` 16-byte aligned)
 hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
                         void *out, uint32_t elem_bytes);
-// supplied witnesses, the same transpose the other way: [count][n_wit][elem_bytes] -> V[w2s[k]][first + j], entry 0 excepted;
-// CW_ST_BAD_WITNESS into status[first + j] for a value that is not canonical or an entry 0 that is not 1 (8: `in` 8-byte aligned,
-// 32: 16-byte aligned)
+// supplied witnesses, the same transpose the other way (the kernel of cwk64_ingest_tiled, cw64_transpose_in_kernel, with the
+// witness list for the slots): [count][n_wit][elem_bytes] -> V[w2s[k]][first + j], entry 0 excepted; CW_ST_BAD_WITNESS into
+// status[first + j] for a value that is not canonical or an entry 0 that is not 1 (8: `in` 8-byte aligned, 32: 16-byte aligned)
 hipError_t cwk64_wit_ingest(hipStream_t s, const void *in, void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
                             uint32_t count, uint32_t *status, uint32_t elem_bytes);

@@ -82,4 +82,4 @@ struct FpParams {
 #define CW_ST_ASSERT_FAILED 1u
 #define CW_ST_ARITH 2u
 #define CW_ST_R1CS_FAILED 4u
-#define CW_ST_BAD_WITNESS 8u     // a SUPPLIED witness was malformed (cw64.hip cw64_wit_ingest_kernel); bits 4..7 are unused
+#define CW_ST_BAD_WITNESS 8u     // a SUPPLIED witness was malformed (cw64.hip cw64_transpose_in_kernel<EB, true>); bits 4..7 are unused

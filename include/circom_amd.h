@@ -158,7 +158,7 @@ int cw_set_inputs_device(cw_batch *b, const void *d_le32);
  *   lifetime   cw_set_inputs_n8 copies and synchronises before it returns; d_le8 is read by cw_run in stream order and
  *              must stay unmodified until that run has finished (the rule of cw_set_inputs_device).
  *   size       64-bit runtime: from CW64_INGEST_TILE_MIN inputs upwards (cw_host.cpp, a measured threshold), and always beyond
- *              65 535 inputs, both element sizes enter through one tiled transpose (cw64.hip cw64_ingest_tiled_kernel), which
+ *              65 535 inputs, both element sizes enter through one tiled transpose (cw64.hip cw64_transpose_in_kernel), which
  *              has no limit on the number of inputs.  Only a 32-byte image at an address that is no multiple of 16 is still
  *              limited to 65 535 inputs (CW_EDEVICE from cw_run).
  * Any other setter puts the batch back on the 32-byte form.  CW64_INGEST_TILED=0 / 1, read at cw_batch_create, forces the
@@ -252,7 +252,7 @@ int cw_write_wtnsb(cw_batch *b, const char *path);
  * on them - the batch counterpart of `snarkjs wtns check`.  The image is [count][n_witness][element] little-endian in the order
  * of the circuit's witness list (cw_set_witness_list), element = 32 bytes (cw_set_witnesses, _device) or cw_element_bytes = 8
  * (the _n8 forms, the files); instance j of the image is instance first + j of the batch.  One tiled transpose on the device
- * (csrc/cw64.hip cw64_wit_ingest_kernel), the mirror image of the bulk egress.
+ * (csrc/cw64.hip cw64_transpose_in_kernel<EB, true>), the mirror image of the bulk egress.
  *   validation  nothing is repaired quietly.  The value stored is the reduced one (the check needs a residue), and
  *               CW_ST_BAD_WITNESS is set in the instance's status word when a value was not canonical (>= p; in the 32-byte
  *               form also: any of the upper three words set) or entry 0 is not 1.  Entry 0 is not stored: the constant wire

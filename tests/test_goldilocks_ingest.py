@@ -1,5 +1,5 @@
 """Bulk ingest of the 64-bit runtime (`--prime goldilocks`): cw_set_inputs_n8 / cw_set_inputs_device_n8 (8 bytes per value) and the
-tiled-transpose ingest kernel behind both element sizes (csrc/cw64.hip cw64_ingest_tiled_kernel; CW64_INGEST_TILED=0 keeps
+tiled-transpose ingest kernel behind both element sizes (csrc/cw64.hip cw64_transpose_in_kernel; CW64_INGEST_TILED=0 keeps
 cw64_ingest_kernel, =1 forces the transpose wherever the image's alignment allows it).
 
 Expected values come from the reference's own 64-bit runtime (tests/golden/reference_wtns_goldilocks.json), from the oracle

@@ -1,6 +1,6 @@
 """Supplied witnesses on the 64-bit runtime (`--prime goldilocks`): cw_set_witnesses(_n8)(_device)(_n8), cw_read_wtns(_many),
 cw_witnesses_missing and `cw_witness --check` - witnesses this batch did not compute go INTO the value table (csrc/cw64.hip
-cw64_wit_ingest_kernel, the bulk egress transpose the other way, scattering through the witness list) and cw_check_r1cs,
+cw64_transpose_in_kernel<EB, true>, the bulk egress transpose the other way, scattering through the witness list) and cw_check_r1cs,
 cw_explain and every egress work on them.
 
 Expected values come from the reference's own 64-bit runtime (tests/golden/reference_wtns_goldilocks.json) or from the oracle

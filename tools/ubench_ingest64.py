@@ -4,8 +4,8 @@
       x[n] inputs;  s[0] <== x[0];  s[k] <== s[k-1] * x[k] + x[k];  out <== s[n-1]
 
   (a) 32-byte image, CW64_INGEST_TILED=0: cw64_ingest_kernel<32> (lane = instance, one grid row per input)
-  (b) 32-byte image, CW64_INGEST_TILED=1: cw64_ingest_tiled_kernel<32> (tiled transpose through LDS)
-  (c) 8-byte image,  CW64_INGEST_TILED=1: cw64_ingest_tiled_kernel<8>
+  (b) 32-byte image, CW64_INGEST_TILED=1: cw64_transpose_in_kernel<32, false> (tiled transpose through LDS)
+  (c) 8-byte image,  CW64_INGEST_TILED=1: cw64_transpose_in_kernel<8, false>
   (d) 8-byte image,  CW64_INGEST_TILED=0: cw64_ingest_kernel<8>
   (e) 32-byte image, CW64_INGEST_TILED unset: the kernel the library picks by itself (CW64_INGEST_TILE_MIN)
   (f) 8-byte image,  CW64_INGEST_TILED unset

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Supplied witnesses of the 64-bit runtime timed on Poseidon(2) over Goldilocks x 65 536 (1 108 entries per witness):
 
-  (a) cw_set_witnesses_device_n8, 8-byte elements:  cw64_wit_ingest_kernel<8>
-  (b) cw_set_witnesses_device,    32-byte elements: cw64_wit_ingest_kernel<32>
+  (a) cw_set_witnesses_device_n8, 8-byte elements:  cw64_transpose_in_kernel<8, true>
+  (b) cw_set_witnesses_device,    32-byte elements: cw64_transpose_in_kernel<32, true>
   (y) the yardstick from the same run: cw64_egress_kernel for the same ranges, cw_get_witnesses_device_n8 / cw_get_witnesses_device
 
 One batch is evaluated and its witnesses streamed out (8-byte and 32-byte image); a second batch of the same circuit takes them
