@@ -504,6 +504,68 @@ cw_bits_collect_inputs_kernel(const uint64_t *__restrict__ masks, const uint4 *_
     out[((size_t)j * n_in + k) * 2 + 1] = hi;
 }
 
+// Boolean inputs as packed ROWS (cw_set_inputs_rows*): what a caller holds is the bytes of each instance's message, instance
+// after instance; what cw_bits_ingest_packed_kernel reads is the transpose, masks[group][k] with bit i = input k of instance
+// 64 group + i.  `rows`: 8-byte aligned, row j at rows + j * stride_w words, input k of a row = bit k & 63 of word k >> 6 once the
+// bits of each byte are in ascending order (MSB: they arrive the other way round, most significant bit first).  This is the tiled
+// transpose of cw64.hip (cw64_transpose_in_kernel<8, false>) with a 64 x 64 bit matrix in the write stage.  A workgroup of four
+// waves owns 64 instances (one group, blockIdx.x: no 65 535 limit on the instances) x 64 words = 4 096 inputs (blockIdx.y):
+//   read       wave w takes the instances w, w + 4, ... of the tile; its 64 lanes read 64 consecutive words of ONE row, 512
+//              contiguous bytes per load.  The 16 loads of a wave stand in one straight-line block under the lane's own
+//              condition (the row bases are wave-uniform); the last instance tile of a batch has a row condition too and takes
+//              that slower form.  Words past ceil(n_in / 64) and rows past `batch` are not read and count as 0.
+//   stage      tile[instance][word] in LDS with rows of 65 words of 8 bytes, as cw64_egress_kernel's tile.  Row-wise write
+//              (ds_write_b64: four groups of 16 consecutive lanes, bank = (a/4) % 32): a group writes 16 consecutive words = 32
+//              consecutive dwords, every bank once, whatever the row's start.  Column-wise read (ds_read_b64: two groups of 32
+//              lanes, bank = (a/4) % 64): lane l reads word 65 l + w, dwords 130 l + 2 w and the next one, bank pair
+//              2 ((l + w) % 32): the 32 rows l of a group fall on distinct pairs.  With rows of 64 words every lane of a group
+//              would hit pair 2 (w % 32): 32-way.  Zero conflicts in both directions - by this arithmetic from the documented
+//              bank rules; no bank-conflict counter pass was taken on this kernel.
+//   transpose  wave w takes the words w, w + 4, ...; lane i holds word x of instance i.  MSB first: the bits inside each byte are
+//              reversed (bit-reverse the word, then swap its bytes back).  For k = 0 .. 63 the ballot of bit k of x over the wave
+//              IS masks[group][64 word + k], bit i = instance 64 group + i; it is wave-uniform, and lane k keeps it (two selects
+//              under lane == k; the compiler forms the 64 lane conditions once, ahead of the loop).  Lanes of instances past the batch hold 0, so the last group's upper bits are 0.
+//   write      lane k stores its mask: 64 consecutive entries of masks[group][...], one 512-byte store per word.  Lanes whose
+//              input index is >= n_in store nothing.
+// Kept apart from the 64-bit transpose on purpose: a shared write stage cost that kernel 24 VGPRs (NOTES).
+#define ROWS_S 65
+template <bool MSB>
+__global__ void __launch_bounds__(256)
+cw_bits_rows_to_masks_kernel(const uint64_t *__restrict__ rows, size_t stride_w, uint32_t n_in, uint32_t batch, uint64_t *__restrict__ masks) {
+    __shared__ uint64_t tile[64 * ROWS_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t g = blockIdx.x, w0 = blockIdx.y * 64u;
+    const uint32_t n_words = (n_in >> 6) + ((n_in & 63u) != 0);
+    const uint32_t nw = n_words - w0 < 64u ? n_words - w0 : 64u, nj = batch - g * 64u < 64u ? batch - g * 64u : 64u;
+    const uint64_t *t0 = rows + (size_t)g * 64u * stride_w + w0;
+    uint64_t v[64 / 4] = {};
+    if (lane < nw) {
+        if (nj == 64u) {
+#pragma unroll
+            for (uint32_t i = 0; i < 64 / 4; i++) v[i] = t0[(size_t)(wave + 4 * i) * stride_w + lane];
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 64 / 4; i++)
+                if (wave + 4 * i < nj) v[i] = t0[(size_t)(wave + 4 * i) * stride_w + lane];
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 64 / 4; i++) tile[(wave + 4 * i) * ROWS_S + lane] = v[i];
+    __syncthreads();
+    for (uint32_t w = wave; w < nw; w += 4) {                          // wave-uniform: every lane takes part in the ballots
+        uint64_t x = tile[lane * ROWS_S + w];
+        if (MSB) x = __builtin_bswap64(__builtin_bitreverse64(x));
+        uint64_t keep = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 64; k++) {
+            const uint64_t m = __builtin_amdgcn_ballot_w64((x >> k) & 1u);
+            if (lane == k) keep = m;
+        }
+        const uint64_t k = (uint64_t)(w0 + w) * 64u + lane;
+        if (k < n_in) masks[(size_t)g * n_in + k] = keep;
+    }
+}
+
 // ---- R1CS check on the bit table ---------------------------------------------------------------------------------------------
 // Class E: constraints over <= 5 distinct wires.  The host enumerated A*B - C over the 2^k assignments of the wires
 // (cw_host.cpp, exact integer arithmetic): the constraint is a 32-entry truth table "violated?".  A vrow checks 64
@@ -808,6 +870,21 @@ hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void 
                            (const uint4 *)aos, inst + done, n, n_in, (uint4 *)out + (size_t)done * n_in * 2);
         return hipGetLastError();
     });
+}
+// groups in gridDim.x (2^31 - 1 of them), word tiles of 4 096 inputs in gridDim.y: one launch, no walk over pieces
+hipError_t cwk_bits_rows_to_masks(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *d_masks) {
+    if (n_in == 0 || batch == 0) return hipSuccess;
+    const uint32_t n_words = (n_in >> 6) + ((n_in & 63u) != 0);
+    if (((uintptr_t)d_rows & 7) || (stride & 7) || stride / 8 < n_words) return hipErrorInvalidValue;
+    const dim3 grid((batch >> 6) + ((batch & 63u) != 0), (n_words + 63) / 64);
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    if (msb)
+        hipLaunchKernelGGL(cw_bits_rows_to_masks_kernel<true>, grid, dim3(256), 0, s, (const uint64_t *)d_rows, stride / 8, n_in, batch,
+                           (uint64_t *)d_masks);
+    else
+        hipLaunchKernelGGL(cw_bits_rows_to_masks_kernel<false>, grid, dim3(256), 0, s, (const uint64_t *)d_rows, stride / 8, n_in, batch,
+                           (uint64_t *)d_masks);
+    return hipGetLastError();
 }
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,

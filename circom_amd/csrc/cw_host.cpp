@@ -22,6 +22,7 @@
 #include "cw_devbuf.h"
 #include "cw_rerun.h"
 #include "cw_pieces.h"
+#include "cw_rows.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
 
@@ -2387,22 +2388,104 @@ extern "C" int cw_set_inputs_bits_device(cw_batch *b, const void *d_masks) {
     set_input_source(b, nullptr, d_masks, 32, false);
     return CW_OK;
 }
+// a buffer of their own: the masks are 1 bit per input and instance, the 32-byte staging image (d_in) 256 times that - 226 GB
+// for 2^18 instances of the 27 008-input SHA-256, which the masks must not need
+static int ensure_d_pmask(cw_batch *b, size_t *n_bytes) {
+    const size_t nbytes = std::max<size_t>((size_t)b->n_groups * b->c->n_inputs * 8, 8);
+    hipError_t e = b->d_pmask.grow(nbytes);
+    if (e != hipSuccess) return fail(CW_EDEVICE, "hipMalloc of the packed input masks failed (" + std::to_string(nbytes) + " bytes): " + hipGetErrorString(e));
+    if (n_bytes) *n_bytes = nbytes;
+    return CW_OK;
+}
+static uint32_t piece_rows(size_t row, uint32_t count);
 extern "C" int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks) {
     if (!b || !masks) return fail(CW_EINVAL, "null argument");
     NOT_FOR_64(b, "packed boolean inputs");
     NEED_DEVICE(b);
     if (!b->bitmode) return fail(CW_ESTATE, "packed boolean inputs need a bit-plane batch (cw_batch_bitmode)");
     HIPCHK(hipSetDevice(b->device));
-    // a buffer of their own: the masks are 1 bit per input and instance, the 32-byte staging image (d_in) 256 times that - 226 GB
-    // for 2^18 instances of the 27 008-input SHA-256, which the masks must not need
-    const size_t nbytes = std::max<size_t>((size_t)b->n_groups * b->c->n_inputs * 8, 8);
-    {
-        hipError_t e = b->d_pmask.grow(nbytes);
-        if (e != hipSuccess) return fail(CW_EDEVICE, "hipMalloc of the packed input masks failed (" + std::to_string(nbytes) + " bytes): " + hipGetErrorString(e));
-    }
+    size_t nbytes = 0;
+    if (int rc = ensure_d_pmask(b, &nbytes)) return rc;
     HIPCHK(hipMemcpyAsync(b->d_pmask, masks, nbytes, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return cw_set_inputs_bits_device(b, b->d_pmask);
+}
+
+// ---- boolean inputs as packed rows (cw_rows.h) ----
+// The bytes a caller holds - each instance's message, instance after instance - become the batch's own bulk inputs on the device,
+// INSIDE the call and in stream order (the rule of the supplied-witness calls, not the deferred one of cw_set_inputs_device):
+//   bit-plane batches  the bit transpose of cw_bits.hip writes masks[groups][n_inputs] into d_pmask, and the batch goes on as after
+//                      cw_set_inputs_bits_device(b, d_pmask): ingest, side batch and the graph key of cw_run_check read packed_in
+//   the other engines  cw_rows_expand_kernel writes d_in as the image [batch][n_inputs][EB] of values 0 / 1 (EB = 8 for the
+//                      64-bit runtime, else 32), which cw_run ingests through the kernels it has
+// Checks in the order of the supplied-witness calls: null / range / flags / alignment (CW_EINVAL), then the device.
+static_assert(CW_ROWS_MSB_FIRST == CW_ROWS_FLAG_MSB, "cw_rows.h names the flag of include/circom_amd.h");
+static int rows_args(cw_batch *b, const void *rows, size_t stride, uint32_t flags, bool device) {
+    if (!b || !rows) return fail(CW_EINVAL, "null argument");
+    const char *why = device ? cw_rows_check_device(rows, stride, b->c->n_inputs) : cw_rows_check_host(stride, b->c->n_inputs);
+    if (!why) why = cw_rows_check_flags(flags);
+    if (why) return fail(CW_EINVAL, std::string(device ? "cw_set_inputs_rows_device: " : "cw_set_inputs_rows: ") + why);
+    return CW_OK;
+}
+static uint32_t rows_eb(const cw_batch *b) { return b->c->is64 ? 8 : 32; }
+// the batch's own buffer the converted inputs go to
+static int rows_target(cw_batch *b) {
+    HIPCHK(hipSetDevice(b->device));
+    return b->bitmode ? ensure_d_pmask(b, nullptr) : ensure_d_in(b);
+}
+// one launch for the instances first .. first + count (first a multiple of 64) from DEVICE rows of whole 8-byte words
+static int rows_convert(cw_batch *b, const void *d_rows, size_t stride, bool msb, uint32_t first, uint32_t count) {
+    const uint32_t n = b->c->n_inputs;
+    if (b->bitmode)
+        HIPCHK(cwk_bits_rows_to_masks(b->stream, d_rows, stride, n, count, msb, (uint64_t *)b->d_pmask.get() + (size_t)(first / 64) * n));
+    else
+        HIPCHK(cwk_rows_expand(b->stream, d_rows, stride, n, count, msb, (uint8_t *)b->d_in.get() + (size_t)first * n * rows_eb(b), rows_eb(b)));
+    return CW_OK;
+}
+static void rows_done(cw_batch *b) {
+    if (b->bitmode) set_input_source(b, nullptr, b->d_pmask, 32, false);
+    else set_input_source(b, nullptr, nullptr, rows_eb(b), false);
+}
+extern "C" int cw_set_inputs_rows_device(cw_batch *b, const void *d_rows, size_t stride, uint32_t flags) {
+    if (int rc = rows_args(b, d_rows, stride, flags, true)) return rc;
+    NEED_DEVICE(b);
+    if (int rc = rows_target(b)) return rc;
+    if (int rc = rows_convert(b, d_rows, stride, flags & CW_ROWS_MSB_FIRST, 0, b->batch)) return rc;
+    rows_done(b);
+    return CW_OK;
+}
+// host rows of any stride and alignment: repacked into rows of whole 8-byte words (cw_rows_repack) and staged through d_bulk in
+// pieces of whole groups of 64 instances, synchronised before the staging buffers are written again and before returning, as
+// supply_host / cw_set_inputs_n8 do.  A host-only batch stages each bit as a 32-byte value 0 / 1, as set_inputs_host does.
+extern "C" int cw_set_inputs_rows(cw_batch *b, const uint8_t *rows, size_t stride, uint32_t flags) {
+    if (int rc = rows_args(b, rows, stride, flags, false)) return rc;
+    const uint32_t n = b->c->n_inputs;
+    const bool msb = flags & CW_ROWS_MSB_FIRST;
+    if (b->device < 0) {
+        ensure_host_staging(b);
+        std::fill(b->h_in.begin(), b->h_in.end(), 0);
+        for (size_t j = 0; j < b->batch; j++)
+            for (uint32_t k = 0; k < n; k++) b->h_in[(j * n + k) * 32] = (uint8_t)cw_rows_bit(rows + j * stride, k, msb);
+        std::fill(b->assigned.begin(), b->assigned.end(), 1);
+        set_input_source(b, nullptr, nullptr, 32, true);
+        return CW_OK;
+    }
+    if (int rc = rows_target(b)) return rc;
+    const size_t row = 8 * cw_rows_words(n);
+    uint32_t per = piece_rows(row, b->batch);
+    if (per < b->batch) per = std::max(64u, per & ~63u);
+    std::vector<uint8_t> img(n ? (size_t)per * row : 0);
+    if (n) HIPCHK(b->d_bulk.grow((size_t)per * row));
+    const int rc = cw_pieces(n ? b->batch : 0, per, [&](uint32_t done, uint32_t m) {
+        cw_rows_repack(rows + (size_t)done * stride, stride, n, m, img.data());
+        HIPCHK(hipMemcpyAsync(b->d_bulk, img.data(), (size_t)m * row, hipMemcpyHostToDevice, b->stream));
+        if (int rc2 = rows_convert(b, b->d_bulk, row, msb, done, m)) return rc2;
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return CW_OK;
+    });
+    if (rc) return rc;
+    rows_done(b);
+    return CW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

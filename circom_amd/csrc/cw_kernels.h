@@ -51,6 +51,14 @@ hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uin
                                   uint32_t batch);
 hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void *aos, const uint32_t *inst, uint32_t n_inst,
                                    uint32_t n_in, void *out);
+// boolean inputs as packed rows (cw_set_inputs_rows*, cw_rows.h): d_rows 8-byte aligned, stride a multiple of 8 and at least
+// 8 * ceil(n_in / 64); input k of instance j = bit k & 7 (msb: 7 - (k & 7)) of byte k >> 3 of row j.
+//   cwk_bits_rows_to_masks  the bit transpose into masks[ceil(batch / 64)][n_in], the form cwk_bits_ingest_packed reads
+//   cwk_rows_expand         (cw_kernels.hip; any stride >= ceil(n_in / 8), any alignment of d_rows) the image [batch][n_in][elem_bytes]
+//                           of values 0 / 1, elem_bytes = 8 or 32, `out` 16-byte aligned: what cwk64_ingest* / cwk_ingest read
+hipError_t cwk_bits_rows_to_masks(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *d_masks);
+hipError_t cwk_rows_expand(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *out,
+                           uint32_t elem_bytes);
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,
                          uint32_t n_ichunks, const uint32_t *iterms, const uint32_t *itab, const uint32_t *irow_orig, const void *T,

@@ -1194,6 +1194,44 @@ hipError_t cwk_fill32(hipStream_t s, uint32_t *p, uint32_t v, size_t n) {
     hipLaunchKernelGGL(cw_fill32_kernel, dim3((unsigned)((n + CW_BLOCK - 1) / CW_BLOCK)), dim3(CW_BLOCK), 0, s, p, v, n);
     return hipGetLastError();
 }
+// Boolean inputs as packed rows (cw_set_inputs_rows*, cw_rows.h) for the engines that ingest an image of values: input k of
+// instance j is one bit of rows[j * stride + (k >> 3)] and becomes the EB-byte value 0 / 1 at out[j][k] - the image cw_run's own
+// ingest kernels take (EB = 8: the 64-bit runtime, 32: the 256-bit schedule).  One thread per (instance, input), consecutive
+// threads on consecutive inputs: a wave reads 8 bytes of a row and writes 64 x EB contiguous bytes.  Correct and simple, not a
+// hot path: the bit-plane batches have the transposing kernel of cw_bits.hip.
+template <int EB>
+__global__ void __launch_bounds__(CW_BLOCK) cw_rows_expand_kernel(const uint8_t *__restrict__ rows, size_t stride, uint32_t n_in, uint32_t batch,
+                                                                  uint32_t msb, uint8_t *__restrict__ out) {
+    const uint64_t total = (uint64_t)batch * n_in;
+    for (uint64_t t = (uint64_t)blockIdx.x * CW_BLOCK + threadIdx.x; t < total; t += (uint64_t)gridDim.x * CW_BLOCK) {
+        const uint64_t j = t / n_in;
+        const uint32_t k = (uint32_t)(t - j * n_in);
+        const uint32_t bit = (rows[j * stride + (k >> 3)] >> (msb ? 7u - (k & 7u) : (k & 7u))) & 1u;
+        if (EB == 8) {
+            ((uint64_t *)out)[t] = bit;
+        } else {
+            uint4 *o = (uint4 *)out + t * 2;
+            o[0] = make_uint4(bit, 0, 0, 0);
+            o[1] = make_uint4(0, 0, 0, 0);
+        }
+    }
+}
+hipError_t cwk_rows_expand(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *out,
+                           uint32_t elem_bytes) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if (stride < ((size_t)n_in + 7) / 8 || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)batch * n_in;
+    if (!total) return hipSuccess;
+    const uint64_t need = (total + CW_BLOCK - 1) / CW_BLOCK;
+    const uint32_t blocks = need < (1u << 20) ? (uint32_t)need : 1u << 20;     // grid-stride beyond that
+    if (elem_bytes == 8)
+        hipLaunchKernelGGL(cw_rows_expand_kernel<8>, dim3(blocks), dim3(CW_BLOCK), 0, s, (const uint8_t *)d_rows, stride, n_in, batch, msb ? 1u : 0u,
+                           (uint8_t *)out);
+    else
+        hipLaunchKernelGGL(cw_rows_expand_kernel<32>, dim3(blocks), dim3(CW_BLOCK), 0, s, (const uint8_t *)d_rows, stride, n_in, batch, msb ? 1u : 0u,
+                           (uint8_t *)out);
+    return hipGetLastError();
+}
 hipError_t cwk_fused_merge(hipStream_t s, const uint32_t *found, uint32_t batch, uint32_t *status, uint32_t *first_bad) {
     hipLaunchKernelGGL(cw_fused_merge_kernel, blocks_for(batch), dim3(CW_BLOCK), 0, s, found, batch, status, first_bad);
     return hipGetLastError();

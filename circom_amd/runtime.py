@@ -17,6 +17,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["CW_LIB"]).resolve() if os.environ.get("CW_LIB") else _HERE / "lib" / "libcircom_amd.so"   # CW_LIB: diagnostics builds
 
 ST_OK, ST_ASSERT_FAILED, ST_ARITH, ST_R1CS_FAILED, ST_BAD_WITNESS = 0, 1, 2, 4, 8
+ROWS_MSB_FIRST = 1      # CW_ROWS_MSB_FIRST
 
 
 class CwError(RuntimeError):
@@ -31,7 +32,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -81,6 +82,8 @@ _SIGS = {
     "cw_set_inputs_device_n8": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_bits": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_bits_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cw_set_inputs_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_set_inputs_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
     "cw_stream_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_signal_slots": (C.POINTER(C.c_uint32), [C.c_void_p]),
     "cw_batch_signal_slots": (C.POINTER(C.c_uint32), [C.c_void_p]),
@@ -309,6 +312,20 @@ class Batch:
 
     def set_inputs_bits_device(self, dptr: int):
         _chk(lib().cw_set_inputs_bits_device(self.h, C.c_void_p(dptr)))
+
+    def set_inputs_rows(self, arr, msb_first: bool = True):
+        """boolean inputs as packed rows, every engine (cw_set_inputs_rows): a C-contiguous uint8 array [batch][>= ceil(n_inputs / 8)],
+        row j = the inputs of instance j, input k = bit 7 - (k & 7) of byte k >> 3 (msb_first: np.unpackbits' order, a SHA-256
+        message as it stands) or bit k & 7.  The row stride is the array's."""
+        assert isinstance(arr, np.ndarray) and arr.dtype == np.uint8 and arr.ndim == 2, "a 2-D uint8 array"
+        assert arr.flags["C_CONTIGUOUS"], "the rows must be C-contiguous"
+        assert arr.shape[0] == self.n, arr.shape                      # (a row that is too short is the library's CW_EINVAL)
+        _chk(lib().cw_set_inputs_rows(self.h, arr.ctypes.data_as(C.c_void_p), arr.shape[1], ROWS_MSB_FIRST if msb_first else 0))
+
+    def set_inputs_rows_device(self, dptr: int, stride: int, msb_first: bool = True):
+        """the same from device memory: 8-byte aligned, stride a multiple of 8 and >= 8 * ceil(n_inputs / 64); converted inside the
+        call in stream order (cw_set_inputs_rows_device)"""
+        _chk(lib().cw_set_inputs_rows_device(self.h, C.c_void_p(dptr), stride, ROWS_MSB_FIRST if msb_first else 0))
 
     def stream_witnesses_device(self, first: int, count: int, chunk: int, d_buf0: int, d_buf1: int, consume):
         """consume(first, count, d_chunk, stream) -> int, called once per chunk (cw_stream_witnesses_device)"""

@@ -174,6 +174,28 @@ int cw_set_inputs_device_n8(cw_batch *b, const void *d_le8);
  * 64-bit runtime (--prime goldilocks) - the only entry points that runtime does not serve. */
 int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks);
 int cw_set_inputs_bits_device(cw_batch *b, const void *d_masks);
+/* Boolean inputs as packed ROWS, every engine: the bytes a caller holds.  Instance j's inputs are the first ceil(n_inputs / 8)
+ * bytes of rows + j * stride; input k (main-input slot order, as in the other bulk forms) is bit k & 7 of byte k >> 3, or, with
+ * CW_ROWS_MSB_FIRST, bit 7 - (k & 7): the order of numpy's unpackbits and the order in which circomlib's SHA-256 reads a message,
+ * so a caller of a Sha256(n) circuit passes the messages themselves.  Bits past n_inputs and bytes of a row past
+ * ceil(n_inputs / 8) are ignored; any other flag bit is CW_EINVAL; n_inputs == 0 is CW_OK.  Both calls mark every input of every
+ * instance as set.  The masks above are the TRANSPOSE of this layout; here the device transposes.
+ *   host form    any stride >= ceil(n_inputs / 8), any alignment; copies in pieces and synchronises before it returns.  On a
+ *                host-only batch each bit is staged as a 32-byte value 0 / 1 (cw_get_staged_input returns the bit).
+ *   device form  d_rows 8-byte aligned, stride a multiple of 8 and at least 8 * ceil(n_inputs / 64) - the last 8-byte word of a
+ *                row lies inside the row -, CW_EINVAL otherwise (the pointer is not touched).  The conversion kernel is launched
+ *                INSIDE the call, in stream order: the buffer may be reused once the batch's stream has passed the call - the rule
+ *                of cw_set_witnesses_device, not the deferred one of cw_set_inputs_device.  A host-only batch answers CW_EDEVICE
+ *                after the argument checks.
+ *   engines      bit-plane batches: one tiled bit transpose (csrc/cw_bits.hip cw_bits_rows_to_masks_kernel) writes the batch's own
+ *                masks, and the batch continues as after cw_set_inputs_bits_device.  64-bit runtime and 256-bit schedule: the bits
+ *                are expanded to the batch's own image of values 0 / 1 (8 / 32 bytes each), which cw_run ingests as it ingests
+ *                cw_set_inputs_n8 / cw_set_inputs - correct and simple, one value per bit; a caller who does not know which engine
+ *                cw_batch_create picked can rely on this form.
+ * Every call checks in this order: null / range / flags / alignment (CW_EINVAL), then the device. */
+#define CW_ROWS_MSB_FIRST 1u
+int cw_set_inputs_rows(cw_batch *b, const uint8_t *rows, size_t stride, uint32_t flags);
+int cw_set_inputs_rows_device(cw_batch *b, const void *d_rows, size_t stride, uint32_t flags);
 /* read back input k (slot cw_input_start()+k) of one instance as staged by the two per-signal setters */
 int cw_get_staged_input(cw_batch *b, uint32_t instance, uint32_t k, uint8_t out[32]);
 /* getRemaingInputsToBeSet() (calcwit.hpp:50-52) of one instance */
