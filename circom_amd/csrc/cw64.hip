@@ -379,6 +379,60 @@ __global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__rest
     }
 }
 
+// Witness bits as packed rows (cw_get_witness_rows*): entry k of the list (w2s points at the range's first entry) of instance
+// first + j becomes bit k & 63 of word k >> 6 of rows[j] (MSB: the bits of each byte the other way round), 1 if and only if the
+// value is 1.  The shape of the egress kernel above: a workgroup of four waves owns 64 instances (blockIdx.x: no 65 535 limit on
+// the instances) x 64 words = 4 096 entries (blockIdx.y).
+//   read    lane = instance.  Wave w takes the words w, w + 4, ... of the tile and makes, per word, 64 reads of V[w2s[entry]][instance]:
+//           the slot is wave-uniform, every read 512 contiguous bytes, 16 of them issued before the first value is used; the word is
+//           the OR of (v == 1) << k.  The last word of a range stops at its last entry: the pad bits are 0.
+//   report  a value > 1 gives bit 0; after a ballot one lane reports the wave's lowest such instance, report0 + j, with atomicMin:
+//           at most one atomic per wave and word.  `word` may be nullptr.
+//   stage   tile[instance][word] with rows of EG_S = 65 words, written column-wise and read row-wise: conflict-free by the bank
+//           rules written out above (ds_write_b64, groups of 16 lanes, bank = (a/4) % 32: lane i writes word 65 i + w, bank pair
+//           2 ((i + w) % 16); ds_read_b64, groups of 32 lanes: 32 consecutive words, every one of the 64 banks once).
+//   write   wave w takes the instances w, w + 4, ...; 64 consecutive words of one row per store, 512 contiguous bytes.
+// Instances past `count` and words past ceil(n / 64) are neither read nor written.
+template <bool MSB>
+__global__ void __launch_bounds__(256) cw64_pack_rows_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n,
+                                                             uint32_t Bp, uint32_t first, uint32_t count, uint32_t report0,
+                                                             uint64_t *__restrict__ rows, size_t stride_w, uint32_t *word) {
+    __shared__ uint64_t tile[64 * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, w0 = blockIdx.y * 64u;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    const uint32_t nw = n_words - w0 < 64u ? n_words - w0 : 64u, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool live = lane < nj;
+    const uint64_t *Vj = V + first + j0 + (live ? lane : 0u);
+    for (uint32_t w = wave; w < nw; w += 4) {
+        const uint32_t k0 = (w0 + w) * 64u, ne = n - k0 < 64u ? n - k0 : 64u;
+        uint64_t acc = 0;
+        bool bad = false;
+        for (uint32_t kb = 0; kb < ne; kb += 16) {
+            uint64_t v[16];
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++) {
+                const uint32_t k = kb + i;
+                const uint32_t slot = w2s[k < ne ? k0 + k : k0];     // always an entry of the range: the scalar load needs no branch
+                v[i] = k < ne && live ? Vj[(size_t)slot * Bp] : 0;
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++) {
+                acc |= (uint64_t)(v[i] == 1) << (kb + i);
+                bad |= v[i] > 1;
+            }
+        }
+        const uint64_t who = __builtin_amdgcn_ballot_w64(bad);
+        if (who && word && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(word, report0 + j0 + lane);
+        if (MSB) acc = __builtin_bswap64(__builtin_bitreverse64(acc));
+        tile[lane * EG_S + w] = acc;
+    }
+    __syncthreads();
+    uint64_t *o = rows + (size_t)j0 * stride_w + w0;
+    if (lane < nw)
+        for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * EG_S + lane];
+}
+
 // The transpose INTO the value table, the egress transpose in the other direction, in two uses:
 //   bulk ingest (WIT = false): [count][n][EB] bytes of inputs, EB = 32 (the boundary's element) or 8 (this runtime's), input k of
 //           instance j into V[slot0 + k][first + j];
@@ -620,4 +674,18 @@ hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint3
                            first + done, n, (uint8_t *)out + (size_t)done * n_wit * elem_bytes);
         return hipGetLastError();
     });
+}
+// packed rows of witness bits: instance tiles in gridDim.x, word tiles of 4 096 entries in gridDim.y: one launch.  `word` (or
+// nullptr) takes an atomicMin of report0 + j for every instance j of the launch that held a value > 1; the caller fills it first.
+hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                           uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    if (((uintptr_t)d_rows & 7) || (stride & 7) || stride / 8 < n_words || ((uintptr_t)d_word & 3)) return hipErrorInvalidValue;
+    const dim3 grid((count >> 6) + ((count & 63u) != 0), (n_words + 63) / 64);
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    const auto kernel = msb ? cw64_pack_rows_kernel<true> : cw64_pack_rows_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8,
+                       d_word);
+    return hipGetLastError();
 }

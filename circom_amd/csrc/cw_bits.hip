@@ -566,6 +566,62 @@ cw_bits_rows_to_masks_kernel(const uint64_t *__restrict__ rows, size_t stride_w,
     }
 }
 
+// Witness bits OUT as packed rows (cw_get_witness_rows*): the transpose above in the other direction.  The table holds entry k of
+// the witness list as one mask per group, bit i = instance 64 group + i; a caller reads rows[instance][entry], entry entry0 + k
+// = bit k & 63 of word k >> 6 of row j (MSB: the bits of each byte the other way round - np.packbits, a SHA-256 digest).
+// `wslot` points at entry0 of the composed map sig_slot o w2s.  A workgroup of four waves owns 64 instances (blockIdx.x: no
+// 65 535 limit on the instances) x 64 words = 4 096 entries (blockIdx.y):
+//   read       wave w takes the words w, w + 4, ... of the tile; lane k loads the mask of entry 64 word + k: one 8-byte read through
+//              wslot and bits_group, so both table layouts are served (sh = 0: the 64 slots are wherever the witness list points;
+//              sh = 5: 256 bytes apart at least).  Instances first + 64 tile .. need not start a group: the two neighbouring
+//              groups are shifted together, as cw_bits_gather_kernel does it, and the second is read only when the range reaches
+//              into it.  Lanes whose entry is >= n hold 0: the pad bits of the last word.
+//   transpose  for i = 0 .. 63 the ballot of bit i of the masks over the wave IS word `word` of instance i: bit k = entry
+//              64 word + k.  It is wave-uniform and lane i keeps it.  MSB first: the bits inside each byte are reversed.
+//   stage      tile[instance][word] in LDS with rows of 65 words, the tile of cw_bits_rows_to_masks_kernel used the other way
+//              round: column-wise WRITE (ds_write_b64: four groups of 16 consecutive lanes, bank = (a/4) % 32; lane i writes word
+//              65 i + w, dwords 130 i + 2 w and the next one, bank pair 2 ((i + w) % 16): the 16 lanes of a group fall on distinct
+//              pairs), row-wise READ (ds_read_b64: two groups of 32 lanes, bank = (a/4) % 64; a group reads 32 consecutive words =
+//              64 consecutive dwords, every bank once).  Zero conflicts by that arithmetic from the documented bank rules; no
+//              bank-conflict counter pass was taken on this kernel.
+//   write      wave w takes the instances w, w + 4, ... of the tile; its lanes store 64 consecutive words of ONE row, 512
+//              contiguous bytes.  Rows of instances past `count` and words past ceil(n / 64) are neither read nor written.
+// A bit table cannot hold a value that is not 0 or 1: this kernel has no word to report through.
+template <bool MSB>
+__global__ void __launch_bounds__(256)
+cw_bits_masks_to_rows_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n,
+                             uint32_t first, uint32_t count, uint64_t *__restrict__ rows, size_t stride_w) {
+    __shared__ uint64_t tile[64 * ROWS_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, w0 = blockIdx.y * 64u;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    const uint32_t nw = n_words - w0 < 64u ? n_words - w0 : 64u, nj = count - j0 < 64u ? count - j0 : 64u;
+    const uint32_t i0 = first + j0, g = i0 >> 6, sh = i0 & 63u;
+    const bool two = sh && 64u - sh < nj;                                  // instance i0 + 64 - sh, the first of group g + 1, is in the range
+    const uint64_t *Tg = bits_group(T, slots, lsh, g), *Tg1 = bits_group(T, slots, lsh, two ? g + 1 : g);
+    for (uint32_t w = wave; w < nw; w += 4) {                              // wave-uniform: every lane takes part in the ballots
+        const uint64_t k = (uint64_t)(w0 + w) * 64u + lane;
+        uint64_t m = 0;
+        if (k < n) {
+            const size_t at = (size_t)wslot[k] << lsh;
+            m = Tg[at] >> sh;
+            if (two) m |= Tg1[at] << (64u - sh);
+        }
+        uint64_t keep = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 64; i++) {
+            const uint64_t x = __builtin_amdgcn_ballot_w64((m >> i) & 1u);
+            if (lane == i) keep = x;
+        }
+        if (MSB) keep = __builtin_bswap64(__builtin_bitreverse64(keep));
+        tile[lane * ROWS_S + w] = keep;
+    }
+    __syncthreads();
+    uint64_t *o = rows + (size_t)j0 * stride_w + w0;
+    if (lane < nw)
+        for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * ROWS_S + lane];
+}
+
 // ---- R1CS check on the bit table ---------------------------------------------------------------------------------------------
 // Class E: constraints over <= 5 distinct wires.  The host enumerated A*B - C over the 2^k assignments of the wires
 // (cw_host.cpp, exact integer arithmetic): the constraint is a 32-entry truth table "violated?".  A vrow checks 64
@@ -884,6 +940,18 @@ hipError_t cwk_bits_rows_to_masks(hipStream_t s, const void *d_rows, size_t stri
     else
         hipLaunchKernelGGL(cw_bits_rows_to_masks_kernel<false>, grid, dim3(256), 0, s, (const uint64_t *)d_rows, stride / 8, n_in, batch,
                            (uint64_t *)d_masks);
+    return hipGetLastError();
+}
+// instance tiles in gridDim.x, word tiles of 4 096 entries in gridDim.y: one launch
+hipError_t cwk_bits_masks_to_rows(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n, uint32_t first,
+                                  uint32_t count, bool msb, void *d_rows, size_t stride) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    if (((uintptr_t)d_rows & 7) || (stride & 7) || stride / 8 < n_words) return hipErrorInvalidValue;
+    const dim3 grid((count >> 6) + ((count & 63u) != 0), (n_words + 63) / 64);
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    const auto kernel = msb ? cw_bits_masks_to_rows_kernel<true> : cw_bits_masks_to_rows_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)T, slots, sh, wslot, n, first, count, (uint64_t *)d_rows, stride / 8);
     return hipGetLastError();
 }
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,

@@ -3381,6 +3381,84 @@ extern "C" int cw_get_public(cw_batch *b, uint8_t *out) {
     return rc;
 }
 
+// ---- witness bits out as packed rows (cw_rows.h) ----
+// The mirror image of cw_set_inputs_rows*: entries [entry0, entry0 + n) of the witness list for the instances [first, first +
+// count) as rows of bits, one kernel per table layout (cw_kernels.h), walking the engines as device_egress does:
+//   64-bit runtime     cw64_pack_rows_kernel reads V64 through the witness list - also in the supplied-witness state
+//   bit-plane batches  cw_bits_masks_to_rows_kernel transposes the table's masks; the rows of the instances the side batch re-ran
+//                      are written over from there, one launch per run of consecutive instances, and a side batch that holds the
+//                      whole batch serves the range alone.  The first egress after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_pack_rows_kernel compares with the table's form of 0 and 1
+// `report0`: the batch's instance index of the launch's first row - a side batch reports in the caller's numbering.
+static int rows_egress(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, uint32_t report0, bool msb, void *d_rows,
+                       size_t stride, uint32_t *d_word) {
+    const cw_circuit *c = b->c;
+    if (c->is64) {
+        HIPCHK(cwk64_pack_rows(b->stream, b->d_V64, b->d_w2s + entry0, n, b->Bp, first, count, report0, msb, d_rows, stride, d_word));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return rows_egress(b->fb, entry0, n, first, count, report0, msb, d_rows, stride, d_word);
+        HIPCHK(cwk_bits_masks_to_rows(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + entry0, n, first, count, msb, d_rows, stride));
+        return cw_rerun_runs(b->fb_inst, first, count, [&](uint32_t pos, uint32_t len, uint32_t off) {
+            return rows_egress(b->fb, entry0, n, pos, len, report0 + off, msb, (char *)d_rows + (size_t)off * stride, stride, d_word);
+        });
+    }
+    HIPCHK(cwk_pack_rows(b->stream, b->d_V, b->d_w2s + entry0, n, b->Bp, first, count, report0, msb, d_rows, stride, d_word, c->mont, c->P));
+    return CW_OK;
+}
+// what both calls check first, in the order of getter_ready: null / range / flags / alignment (CW_EINVAL), the device, the state
+static int rows_out_ready(cw_batch *b, const void *rows, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, size_t stride,
+                          uint32_t flags, const void *d_word, bool device) {
+    if (!b || !rows) return fail(CW_EINVAL, "null argument");
+    const char *why = cw_rows_check_range(entry0, n, b->c->n_witness, first, count, b->batch);
+    if (!why) why = cw_rows_check_flags(flags);
+    if (!why) why = device ? cw_rows_check_device(rows, stride, n) : cw_rows_check_host(stride, n);
+    if (!why && device) why = cw_rows_check_word(d_word);
+    const char *who = device ? "cw_get_witness_rows_device" : "cw_get_witness_rows";
+    if (why) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    NEED_DEVICE(b);
+    if (!b->ran) return fail(CW_ESTATE, std::string(who) + " before cw_run");
+    HIPCHK(hipSetDevice(b->device));
+    return CW_OK;
+}
+extern "C" int cw_get_witness_rows_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, void *d_rows, size_t stride,
+                                          uint32_t flags, void *d_not_boolean) {
+    if (int rc = rows_out_ready(b, d_rows, entry0, n, first, count, stride, flags, d_not_boolean, true)) return rc;
+    if (d_not_boolean) HIPCHK(cwk_fill32(b->stream, (uint32_t *)d_not_boolean, 0xFFFFFFFFu, 1));
+    if (n == 0 || count == 0) return CW_OK;
+    return rows_egress(b, entry0, n, first, count, first, flags & CW_ROWS_MSB_FIRST, d_rows, stride, (uint32_t *)d_not_boolean);
+}
+// Host rows of any stride and alignment: rows of whole 8-byte words are staged in d_bulk piece by piece (cw_pieces / piece_rows, as
+// get_witnesses_host does; the word lives behind the piece), copied to a host image and from there, ceil(n / 8) bytes per row,
+// into the caller's rows (cw_rows_scatter).  Synchronised before the staging buffer is written again and before returning.
+extern "C" int cw_get_witness_rows(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, uint8_t *rows, size_t stride,
+                                   uint32_t flags, uint32_t *not_boolean) {
+    if (int rc = rows_out_ready(b, rows, entry0, n, first, count, stride, flags, nullptr, false)) return rc;
+    if (not_boolean) *not_boolean = 0xFFFFFFFFu;
+    if (n == 0 || count == 0) return CW_OK;
+    const size_t row = 8 * cw_rows_words(n);
+    const uint32_t per = piece_rows(row, count);
+    HIPCHK(b->d_bulk.grow((size_t)per * row + 8));
+    uint32_t *d_word = (uint32_t *)((char *)b->d_bulk.get() + (size_t)per * row);
+    HIPCHK(cwk_fill32(b->stream, d_word, 0xFFFFFFFFu, 1));
+    std::vector<uint8_t> img((size_t)per * row);
+    const int rc = cw_pieces(count, per, [&](uint32_t done, uint32_t m) {
+        if (int rc2 = rows_egress(b, entry0, n, first + done, m, first + done, flags & CW_ROWS_MSB_FIRST, b->d_bulk, row, d_word)) return rc2;
+        HIPCHK(hipMemcpyAsync(img.data(), b->d_bulk, (size_t)m * row, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        cw_rows_scatter(img.data(), n, m, rows + (size_t)done * stride, stride);
+        return CW_OK;
+    });
+    if (rc) return rc;
+    if (not_boolean) {
+        HIPCHK(hipMemcpyAsync(not_boolean, d_word, 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return CW_OK;
+}
+
 extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]) {
     if (!b || !out) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch || slot >= b->c->n_signals) return fail(CW_EINVAL, "instance or slot out of range");

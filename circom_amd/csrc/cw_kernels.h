@@ -59,6 +59,17 @@ hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void 
 hipError_t cwk_bits_rows_to_masks(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *d_masks);
 hipError_t cwk_rows_expand(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *out,
                            uint32_t elem_bytes);
+// witness bits OUT as packed rows (cw_get_witness_rows*, cw_rows.h), one kernel per table layout: entry k of the range (wslot / w2s
+// point at its first entry) of instance first + j = bit k & 7 (msb: 7 - (k & 7)) of byte k >> 3 of d_rows + j * stride, 1 iff the
+// value is 1; rows of 8 * ceil(n / 64) bytes are written, pad bits 0.  d_rows 8-byte aligned, stride a multiple of 8 and at least
+// that.  The two value tables report a value that is neither 0 nor 1 by atomicMin(d_word, report0 + j); d_word may be nullptr, the
+// caller fills it (cwk_fill32) first.  A bit table holds no such value.
+hipError_t cwk_bits_masks_to_rows(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n, uint32_t first,
+                                  uint32_t count, bool msb, void *d_rows, size_t stride);
+hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                           uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word);
+hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word, bool mont, const FpParams &P);
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,
                          uint32_t n_ichunks, const uint32_t *iterms, const uint32_t *itab, const uint32_t *irow_orig, const void *T,

@@ -1035,6 +1035,67 @@ cw_gather_many_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ 
     }
 }
 
+// ---- witness bits as packed rows (cw_get_witness_rows*) -----------------------------------------------------
+// Entry k of the list (w2s points at the range's first entry) of instance first + j becomes bit k & 63 of word k >> 6 of rows[j]
+// (MSB: the bits of each byte the other way round), 1 if and only if the value is 1.  The shape of the 64-bit runtime's kernel
+// (cw64.hip cw64_pack_rows_kernel) over the 8 x u32 table, addressed as cw_gather_many_kernel addresses it: a workgroup of four
+// waves owns 64 instances (blockIdx.x) x 64 words = 4 096 entries (blockIdx.y); lane = instance; wave w takes the words w, w + 4,
+// ... and reads, per entry, the two 16-byte halves of 64 consecutive instances (1 KiB contiguous each, the slot wave-uniform).
+// Nothing is converted: a residue is 0, or it is the table's form of 1 - canonical 1, or R mod q in a Montgomery-form table, which
+// the host passes (one_lo, one_hi) -, or it is not boolean: bit 0, and after a ballot one lane reports the wave's lowest such
+// instance, report0 + j, with atomicMin (at most one atomic per wave and word; `word` may be nullptr).  The words are staged as
+// tile[instance][word] with rows of 65 eight-byte words (column-wise write, row-wise read: conflict-free, the arithmetic stands at
+// cw64_egress_kernel) and every store is 64 consecutive words of one row.  Instances past `count` and words past ceil(n / 64)
+// are neither read nor written.
+template <bool MONT, bool MSB>
+__global__ void __launch_bounds__(256)
+cw_pack_rows_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                    uint32_t report0, uint64_t *__restrict__ rows, size_t stride_w, uint32_t *word, uint4 one_lo, uint4 one_hi) {
+    __shared__ uint64_t tile[64 * 65];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, w0 = blockIdx.y * 64u;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    const uint32_t nw = n_words - w0 < 64u ? n_words - w0 : 64u, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool live = lane < nj;
+    const uint4 *Vj = V + first + j0 + (live ? lane : 0u);
+    if (!MONT) {
+        one_lo = make_uint4(1u, 0u, 0u, 0u);
+        one_hi = make_uint4(0u, 0u, 0u, 0u);
+    }
+    for (uint32_t w = wave; w < nw; w += 4) {
+        const uint32_t k0 = (w0 + w) * 64u, ne = n - k0 < 64u ? n - k0 : 64u;
+        uint64_t acc = 0;
+        bool bad = false;
+        for (uint32_t kb = 0; kb < ne; kb += 8) {
+            uint4 lo[8], hi[8];
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++) {
+                const uint32_t k = kb + i;
+                const size_t base = (size_t)w2s[k < ne ? k0 + k : k0] * 2 * Bp;   // always an entry of the range
+                const bool on = k < ne && live;
+                lo[i] = on ? Vj[base] : make_uint4(0u, 0u, 0u, 0u);
+                hi[i] = on ? Vj[base + Bp] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++) {
+                const uint32_t z = lo[i].x | lo[i].y | lo[i].z | lo[i].w | hi[i].x | hi[i].y | hi[i].z | hi[i].w;
+                const uint32_t d = (lo[i].x ^ one_lo.x) | (lo[i].y ^ one_lo.y) | (lo[i].z ^ one_lo.z) | (lo[i].w ^ one_lo.w) |
+                                   (hi[i].x ^ one_hi.x) | (hi[i].y ^ one_hi.y) | (hi[i].z ^ one_hi.z) | (hi[i].w ^ one_hi.w);
+                acc |= (uint64_t)(d == 0) << (kb + i);
+                bad |= z != 0 && d != 0;
+            }
+        }
+        const uint64_t who = __builtin_amdgcn_ballot_w64(bad);
+        if (who && word && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(word, report0 + j0 + lane);
+        if (MSB) acc = __builtin_bswap64(__builtin_bitreverse64(acc));
+        tile[lane * 65 + w] = acc;
+    }
+    __syncthreads();
+    uint64_t *o = rows + (size_t)j0 * stride_w + w0;
+    if (lane < nw)
+        for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * 65 + lane];
+}
+
 // ---- Fp multiplication micro-benchmark: iters dependent Montgomery products per lane --------------------
 __global__ void __launch_bounds__(CW_BLOCK)
 cw_mulbench_kernel(const uint4 *__restrict__ a, const uint4 *__restrict__ b, uint4 *__restrict__ out, uint32_t n,
@@ -1296,5 +1357,22 @@ hipError_t cwk_fpop(hipStream_t s, uint32_t op, const void *a, const void *b, co
                     uint32_t n, const FpParams &P) {
     hipLaunchKernelGGL(cw_fpop_kernel, blocks_for(n), dim3(CW_BLOCK), 0, s, op, (const uint4 *)a, (const uint4 *)b,
                        (const uint4 *)c, (uint4 *)out, status, n, P);
+    return hipGetLastError();
+}
+// packed rows of witness bits from the 8 x u32 table: instance tiles in gridDim.x, word tiles of 4 096 entries in gridDim.y: one
+// launch.  `word` (or nullptr) takes an atomicMin of report0 + j for every instance j of the launch that held a value other than
+// 0 and the table's 1 (P.one_m = R mod q when `mont`); the caller fills it first.
+hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word, bool mont, const FpParams &P) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const uint32_t n_words = (n >> 6) + ((n & 63u) != 0);
+    if (((uintptr_t)d_rows & 7) || (stride & 7) || stride / 8 < n_words || ((uintptr_t)d_word & 3)) return hipErrorInvalidValue;
+    const dim3 grid((count >> 6) + ((count & 63u) != 0), (n_words + 63) / 64);
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    const uint4 one_lo = make_uint4(P.one_m[0], P.one_m[1], P.one_m[2], P.one_m[3]), one_hi = make_uint4(P.one_m[4], P.one_m[5], P.one_m[6], P.one_m[7]);
+    const auto kernel = mont ? (msb ? cw_pack_rows_kernel<true, true> : cw_pack_rows_kernel<true, false>)
+                             : (msb ? cw_pack_rows_kernel<false, true> : cw_pack_rows_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint4 *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8, d_word,
+                       one_lo, one_hi);
     return hipGetLastError();
 }

@@ -42,3 +42,25 @@ static inline void cw_rows_repack(const uint8_t *rows, size_t stride, uint32_t n
         memset(out + j * row + used, 0, row - used);
     }
 }
+
+// ---- witness bits OUT as packed rows (cw_get_witness_rows*) ----
+// The same row layout for results: entry entry0 + k of the witness list is bit k & 7 (msb: 7 - (k & 7)) of byte k >> 3 of row j,
+// 1 if and only if the value is 1.  The device kernels write rows of whole 8-byte words with zero pad bits; the host form copies
+// the ceil(n / 8) bytes that carry entries out of those into the caller's rows.
+// nullptr, or why the call is CW_EINVAL (64-bit sums: entry0 + n and first + count may pass 2^32).
+static inline const char *cw_rows_check_range(uint32_t entry0, uint32_t n, uint32_t n_witness, uint32_t first, uint32_t count, uint32_t batch) {
+    if ((uint64_t)entry0 + n > n_witness) return "entry range out of the witness list";
+    if ((uint64_t)first + count > batch) return "instance range out of the batch";
+    return nullptr;
+}
+// the word that reports a value which is not 0 or 1: compared, never read; nullptr is allowed
+static inline const char *cw_rows_check_word(const void *d_word) {
+    return (uintptr_t)d_word & 3 ? "the device word must be 4-byte aligned" : nullptr;
+}
+// staged[count][8 * cw_rows_words(n)] -> `count` caller rows of `stride` bytes: exactly ceil(n / 8) bytes of each row are written,
+// every other byte of `rows` stays as it was (a row may end where its allocation ends)
+static inline void cw_rows_scatter(const uint8_t *staged, uint32_t n, size_t count, uint8_t *rows, size_t stride) {
+    const size_t used = cw_rows_bytes(n), row = 8 * cw_rows_words(n);
+    if (!used) return;
+    for (size_t j = 0; j < count; j++) memcpy(rows + j * stride, staged + j * row, used);
+}

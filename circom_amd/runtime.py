@@ -108,6 +108,8 @@ _SIGS = {
     "cw_batch_call_lds": (C.c_uint32, [C.c_void_p]),
     "cw_get_public": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_public_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cw_get_witness_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "cw_get_witness_rows_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "cw_get_signal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "cw_get_r1cs_first_bad": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -447,6 +449,33 @@ class Batch:
     def public_signals_device(self, d_ptr: int) -> None:
         """Same, written to device memory at `d_ptr` (batch * n_public * 32 bytes)."""
         _chk(lib().cw_get_public_device(self.h, C.c_void_p(d_ptr)))
+
+    def witness_rows(self, entry0: int, n: int, first: int = 0, count: int | None = None, msb_first: bool = True):
+        """witness bits as packed rows, every engine (cw_get_witness_rows): (uint8 array [count][ceil(n / 8)], word).  Row j =
+        instance first + j, entry entry0 + k of the witness list = bit 7 - (k & 7) of byte k >> 3 (msb_first: np.packbits' order,
+        a SHA-256 digest as it stands) or bit k & 7; the bit is 1 iff the value is 1.  word: 0xFFFFFFFF, or the lowest instance
+        of the range that held a value other than 0 and 1 (its bit is 0)."""
+        count = self.n - first if count is None else count
+        out = np.zeros((count, (n + 7) // 8), dtype=np.uint8)
+        word = C.c_uint32(0)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the range)
+        ptr = out.ctypes.data_as(C.c_void_p) if out.size else C.cast(C.byref(word), C.c_void_p)
+        _chk(lib().cw_get_witness_rows(self.h, entry0, n, first, count, ptr, out.shape[1], ROWS_MSB_FIRST if msb_first else 0, C.byref(word)))
+        return out, word.value
+
+    def witness_rows_device(self, entry0: int, n: int, first: int, count: int, d_ptr: int, stride: int, msb_first: bool = True,
+                            d_not_boolean: int = 0) -> None:
+        """the same into device memory: d_ptr 8-byte aligned, stride a multiple of 8 and >= 8 * ceil(n / 64), 8 * ceil(n / 64)
+        bytes per row written, pad bits 0; d_not_boolean: 0 or the 4-byte aligned device address of the word; asynchronous on the
+        batch's stream (cw_get_witness_rows_device)"""
+        _chk(lib().cw_get_witness_rows_device(self.h, entry0, n, first, count, C.c_void_p(d_ptr), stride, ROWS_MSB_FIRST if msb_first else 0,
+                                              C.c_void_p(d_not_boolean) if d_not_boolean else None))
+
+    def public_rows(self, msb_first: bool = True):
+        """entries 1 .. n_public of every instance as packed rows: (uint8 [batch][ceil(n_public / 8)], word).  msb_first=False is
+        exactly the layout sharding.pack_bit_rows makes of the 32-byte image; for a Sha256(n) circuit the first 32 bytes of a row
+        with msb_first=True are the digest"""
+        return self.witness_rows(1, self.circuit.n_public, 0, self.n, msb_first)
 
     def witnesses(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """[count][n_witness][32] uint8, canonical little-endian values (bulk egress, one device transpose)."""

@@ -255,6 +255,35 @@ int cw_stream_witnesses_device(cw_batch *b, uint32_t first, uint32_t count, uint
  * [batch][n_public][32]: to host memory, or to device memory for a multi-GPU gather */
 int cw_get_public(cw_batch *b, uint8_t *out);
 int cw_get_public_device(cw_batch *b, void *d_out);
+/* Witness bits OUT as packed ROWS, every engine: the mirror image of cw_set_inputs_rows*.  The call covers the entries
+ * [entry0, entry0 + n) of the witness list (cw_set_witness_list order, as every other egress) for the instances
+ * [first, first + count).  Row j starts at rows + j * stride and belongs to instance first + j; entry entry0 + k is bit k & 7 of
+ * byte k >> 3, or, with CW_ROWS_MSB_FIRST, bit 7 - (k & 7): numpy's packbits and the order of a SHA-256 digest - entries 1 .. 256
+ * of a Sha256(n) batch, most significant bit first, ARE hashlib.sha256(message).digest().  The bit is 1 if and only if the value
+ * is 1: a boolean witness leaves in 1/256 of the bytes of cw_get_witnesses(_device).
+ *   not boolean  a value that is neither 0 nor 1 gives bit 0 and is reported through one word: 0xFFFFFFFF when every value read
+ *                was 0 or 1, else the lowest instance index OF THE BATCH, within the range, that held such a value.
+ *                not_boolean / d_not_boolean may be NULL; the device word must be 4-byte aligned.  The call writes the word
+ *                itself, in stream order: a fill kernel, then atomicMin.
+ *   host form    any stride >= ceil(n / 8), any alignment.  Exactly ceil(n / 8) bytes per row are written, the spare bits of the
+ *                last one are 0, every other byte of `rows` stays as it was.  Copies in pieces and synchronises before it returns.
+ *   device form  d_rows 8-byte aligned, stride a multiple of 8 and at least 8 * ceil(n / 64), CW_EINVAL otherwise (the pointer is
+ *                not touched).  8 * ceil(n / 64) bytes per row are written, pad bits 0; the bytes of a row behind them stay as they
+ *                were.  Asynchronous on the batch's stream - with the one exception of every device egress: the first one after a
+ *                cw_run of a bit-plane batch waits for the evaluation (the instances to re-run are known only then).
+ *   empty        n == 0 or count == 0: CW_OK, no row is written, the word (if given) becomes 0xFFFFFFFF.
+ *   errors       entry0 + n > cw_n_witness, first + count > batch, an unknown flag bit, a stride or an alignment as above:
+ *                CW_EINVAL.  Checked in the order of the other getters: null / range / flags / alignment (CW_EINVAL), then the
+ *                device (a host-only batch: CW_EDEVICE), then the state ("... before cw_run": CW_ESTATE).
+ *   engines      bit-plane batches: one tiled bit transpose of the table's masks (csrc/cw_bits.hip cw_bits_masks_to_rows_kernel,
+ *                both table layouts); the rows of instances the 256-bit side batch re-ran are written over from there.  64-bit
+ *                runtime (csrc/cw64.hip cw64_pack_rows_kernel), also in the supplied-witness state, and the 256-bit schedule
+ *                (csrc/cw_kernels.hip cw_pack_rows_kernel, canonical and Montgomery-form tables): the same tile, a compare per
+ *                value.  A caller who does not know which engine cw_batch_create picked can rely on this form. */
+int cw_get_witness_rows(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, uint8_t *rows, size_t stride,
+                        uint32_t flags, uint32_t *not_boolean);
+int cw_get_witness_rows_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, void *d_rows, size_t stride,
+                               uint32_t flags, void *d_not_boolean);
 /* one signal of one instance (signalValues[slot]) */
 int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]);
 /* writeBinWitness (main.cpp:288-334).  Every write is checked, here and in the two calls below: a file that could not be
@@ -288,7 +317,7 @@ int cw_write_wtnsb(cw_batch *b, const char *path);
  *               cw_run_check: plain or replayed from its graph it begins with the table's init and the ingest of the INPUTS, so
  *               it computes the batch's own witnesses over whatever was supplied.
  *   served      cw_get_status, cw_get_r1cs_first_bad, cw_explain, cw_get_witness(es)(_device)(_n8), cw_stream_witnesses_device,
- *               cw_get_public(_device), cw_write_wtns(_many), cw_write_wtnsb read the table through the witness list and work
+ *               cw_get_public(_device), cw_get_witness_rows(_device), cw_write_wtns(_many), cw_write_wtnsb read the table through the witness list and work
  *               unchanged.  No witness program has run on a supplied table: cw_get_signal of a signal the witness list does not
  *               name and cw_get_log answer CW_ESTATE (temporaries and hidden log values were never written).  With a shortened
  *               witness list the check is meaningful when the .r1cs names listed signals only.
