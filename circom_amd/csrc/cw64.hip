@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "cw_kernels.h"
 #include "cw_pieces.h"
+#include "cw_r1cs_products.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
 #define GL_HALF (GL_P >> 1)
@@ -433,6 +434,58 @@ __global__ void __launch_bounds__(256) cw64_pack_rows_kernel(const uint64_t *__r
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * EG_S + lane];
 }
 
+// R1CS products (cw_get_r1cs_products*): out[j][p][k] = the part's sum of coefficient * w[wire] over the terms of constraint
+// row0 + k in instance first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order:
+// rowptr[3 row + part] .. rowptr[3 row + part + 1] into terms {slot, 0, coefficient lo, hi}.  The shape of the kernels above: a
+// workgroup of four waves owns 64 instances (blockIdx.x) x 64 constraints (blockIdx.y).
+//   sum     lane = instance.  Wave w takes the rows w, w + 4, ... of the tile; a term is one scalar load of 16 bytes and one
+//           512-byte read of V[slot][instance], four of them issued before the first product; gl_mul / gl_add.  An empty part is 0.
+//   stage   tile[instance][row] with rows of EG_S = 65 words, written column-wise and read row-wise: the tile and the bank
+//           arithmetic of cw64_pack_rows_kernel.  One part after the other: the terms of A, B and C are disjoint runs, so nothing
+//           is walked twice and the tile is reused (a barrier on either side of the stores).
+//   write   wave w takes the instances w, w + 4, ...; 64 consecutive rows of one instance and part per store, 512 contiguous bytes.
+// `out` points at the launch's first row in instance `first`'s image; `image_rows` = rows of the whole call (the stride of a part),
+// n_sel = selected parts.  Instances past `count` and rows past n_rows are neither read nor written.
+__global__ void __launch_bounds__(256) cw64_products_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ rowptr,
+                                                            const uint4 *__restrict__ terms, uint32_t parts, uint32_t n_sel, uint32_t row0,
+                                                            uint32_t n_rows, uint32_t image_rows, uint32_t Bp, uint32_t first, uint32_t count,
+                                                            uint64_t *__restrict__ out) {
+    __shared__ uint64_t tile[64 * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, k0 = blockIdx.y * 64u;
+    const uint32_t nk = n_rows - k0 < 64u ? n_rows - k0 : 64u, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool live = lane < nj;
+    const uint64_t *Vj = V + first + j0 + (live ? lane : 0u);
+    uint64_t *o = out + (size_t)j0 * n_sel * image_rows + k0;
+    uint32_t sel = 0;
+    for (uint32_t part = 0; part < 3; part++) {
+        if (!((parts >> part) & 1u)) continue;
+        for (uint32_t k = wave; k < nk; k += 4) {
+            const uint32_t *rp = rowptr + (size_t)(row0 + k0 + k) * 3 + part;
+            const uint32_t t0 = rp[0], t1 = rp[1];
+            uint64_t acc = 0;
+            for (uint32_t t = t0; t < t1; t += 4) {
+                uint4 x[4];
+                uint64_t v[4];
+#pragma unroll
+                for (uint32_t i = 0; i < 4; i++) {
+                    x[i] = terms[t + i < t1 ? t + i : t];            // always a term of the part: the scalar load needs no branch
+                    v[i] = Vj[(size_t)x[i].x * Bp];
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < 4; i++)
+                    if (t + i < t1) acc = gl_add(acc, gl_mul(v[i], ((uint64_t)x[i].w << 32) | x[i].z));
+            }
+            tile[lane * EG_S + k] = acc;
+        }
+        __syncthreads();
+        if (lane < nk)
+            for (uint32_t j = wave; j < nj; j += 4) o[((size_t)j * n_sel + sel) * image_rows + lane] = tile[j * EG_S + lane];
+        __syncthreads();
+        sel++;
+    }
+}
+
 // The transpose INTO the value table, the egress transpose in the other direction, in two uses:
 //   bulk ingest (WIT = false): [count][n][EB] bytes of inputs, EB = 32 (the boundary's element) or 8 (this runtime's), input k of
 //           instance j into V[slot0 + k][first + j];
@@ -688,4 +741,18 @@ hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, ui
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8,
                        d_word);
     return hipGetLastError();
+}
+// R1CS products [count][n_sel][n_rows] of 8-byte residues: instance tiles in gridDim.x, row tiles of 64 in gridDim.y, a range of
+// more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one that failed
+hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, const void *terms, uint32_t parts, uint32_t row0, uint32_t n_rows,
+                          uint32_t Bp, uint32_t first, uint32_t count, void *d_out) {
+    const uint32_t n_sel = cwprod::n_parts(parts);
+    if (n_rows == 0 || count == 0) return hipSuccess;
+    if (n_sel == 0 || (parts & ~cwprod::PART_ALL) || ((uintptr_t)d_out & 7)) return hipErrorInvalidValue;
+    return cwprod::row_pieces(n_rows, cwprod::ROWS64, [&](uint32_t off, uint32_t m) {
+        hipLaunchKernelGGL(cw64_products_kernel, dim3((count >> 6) + ((count & 63u) != 0), cwprod::row_tiles(m, cwprod::ROWS64)), dim3(256), 0, s,
+                           (const uint64_t *)V, rowptr, (const uint4 *)terms, parts, n_sel, row0 + off, m, n_rows, Bp, first, count,
+                           (uint64_t *)d_out + off);
+        return hipGetLastError();
+    });
 }

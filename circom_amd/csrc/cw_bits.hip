@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "cw_kernels.h"
 #include "cw_pieces.h"
+#include "cw_r1cs_products.h"
 #include "fp256.hip.h"
 
 
@@ -622,6 +623,59 @@ cw_bits_masks_to_rows_kernel(const uint64_t *__restrict__ T, uint64_t slots, uin
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * ROWS_S + lane];
 }
 
+// ---- R1CS products from the bit table (cw_get_r1cs_products*) -------------------------------------------------------------
+// out[j][p][k] (32 bytes, canonical) = the part's sum of coefficient * w[wire] over the terms of constraint row0 + k in instance
+// first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order: rowptr[3 row + part]
+// .. rowptr[3 row + part + 1] into terms {bit-table slot, id of the canonical coefficient in cctab (8 words each)}; the slots are
+// the batch's own signal map, so both table layouts are served through bits_group (the constant wire is slot 1, all ones: its
+// term is its coefficient; slot 0 holds the signals that are provably 0).  The tile and the store side of cw_products_kernel
+// (cw_kernels.hip): a workgroup of four waves owns 64 instances x PRB_TILE constraints, lane = instance, wave w the rows w,
+// w + 4, ...  A term is a SCALAR load of the group's mask word - the instances first + 64 tile .. need not start a group: the two
+// neighbouring groups are shifted together as cw_bits_masks_to_rows_kernel does it - and lane i adds `bit i ? c : 0`: no
+// multiplication at all.  Instances the 256-bit side batch re-ran hold garbage here: the host writes them over from there.
+#define PRB_TILE 16
+__global__ void __launch_bounds__(256)
+cw_bits_products_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ rowptr,
+                        const uint2 *__restrict__ terms, const uint32_t *__restrict__ cctab, uint32_t parts, uint32_t n_sel, uint32_t row0,
+                        uint32_t n_rows, uint32_t image_rows, uint32_t first, uint32_t count, uint4 *__restrict__ out, FpParams P) {
+    __shared__ uint4 tile[PRB_TILE][2][65];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, k0 = blockIdx.y * PRB_TILE;
+    const uint32_t nk = n_rows - k0 < PRB_TILE ? n_rows - k0 : PRB_TILE, nj = count - j0 < 64u ? count - j0 : 64u;
+    const uint32_t i0 = first + j0, g = i0 >> 6, sh = i0 & 63u;
+    const bool two = sh && 64u - sh < nj;                                  // instance i0 + 64 - sh, the first of group g + 1, is in the range
+    const uint64_t *Tg = bits_group(T, slots, lsh, g), *Tg1 = bits_group(T, slots, lsh, two ? g + 1 : g);
+    constexpr uint32_t PIECES = 2 * PRB_TILE, PER = 64 / PIECES;
+    const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
+    uint4 *o = out + ((size_t)j0 * n_sel * image_rows + k0) * 2 + piece;
+    uint32_t sel = 0;
+    for (uint32_t part = 0; part < 3; part++) {
+        if (!((parts >> part) & 1u)) continue;
+        for (uint32_t k = wave; k < nk; k += 4) {
+            const uint32_t *rp = rowptr + (size_t)(row0 + k0 + k) * 3 + part;
+            const uint32_t t1 = rp[1];
+            fe acc = fe_zero();
+            for (uint32_t t = rp[0]; t < t1; t++) {
+                const uint2 x = terms[t];
+                const size_t at = (size_t)x.x << lsh;
+                uint64_t m = Tg[at] >> sh;
+                if (two) m |= Tg1[at] << (64u - sh);
+                const bool on = (m >> lane) & 1u;
+                fe w;
+                FE_UNROLL for (int q = 0; q < 8; q++) w.v[q] = on ? cctab[(size_t)x.y * 8 + q] : 0u;
+                acc = fe_add(acc, w, P);
+            }
+            tile[k][0][lane] = make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+            tile[k][1][lane] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+        }
+        __syncthreads();
+        if (e < nk)
+            for (uint32_t ii = wave * PER + sub; ii < nj; ii += 4 * PER) o[((size_t)ii * n_sel + sel) * image_rows * 2] = tile[e][h][ii];
+        __syncthreads();
+        sel++;
+    }
+}
+
 // ---- R1CS check on the bit table ---------------------------------------------------------------------------------------------
 // Class E: constraints over <= 5 distinct wires.  The host enumerated A*B - C over the 2^k assignments of the wires
 // (cw_host.cpp, exact integer arithmetic): the constraint is a 32-entry truth table "violated?".  A vrow checks 64
@@ -953,6 +1007,23 @@ hipError_t cwk_bits_masks_to_rows(hipStream_t s, const void *T, uint64_t slots, 
     const auto kernel = msb ? cw_bits_masks_to_rows_kernel<true> : cw_bits_masks_to_rows_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)T, slots, sh, wslot, n, first, count, (uint64_t *)d_rows, stride / 8);
     return hipGetLastError();
+}
+// R1CS products [count][n_sel][n_rows] of 32-byte canonical residues from the bit table: instance tiles in gridDim.x, row tiles of
+// PRB_TILE in gridDim.y, a range of more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one
+// that failed
+static_assert(PRB_TILE == cwprod::ROWS256, "the row tile of cw_bits_products_kernel");
+hipError_t cwk_bits_products(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *rowptr, const uint32_t *terms,
+                             const uint32_t *cctab, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, void *d_out,
+                             const FpParams &P) {
+    const uint32_t n_sel = cwprod::n_parts(parts);
+    if (n_rows == 0 || count == 0) return hipSuccess;
+    if (n_sel == 0 || (parts & ~cwprod::PART_ALL) || ((uintptr_t)d_out & 15)) return hipErrorInvalidValue;
+    return cwprod::row_pieces(n_rows, PRB_TILE, [&](uint32_t off, uint32_t m) {
+        hipLaunchKernelGGL(cw_bits_products_kernel, dim3((count >> 6) + ((count & 63u) != 0), cwprod::row_tiles(m, PRB_TILE)), dim3(256), 0, s,
+                           (const uint64_t *)T, slots, sh, rowptr, (const uint2 *)terms, cctab, parts, n_sel, row0 + off, m, n_rows, first, count,
+                           (uint4 *)d_out + (size_t)off * 2, P);
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,

@@ -23,6 +23,7 @@
 #include "cw_rerun.h"
 #include "cw_pieces.h"
 #include "cw_rows.h"
+#include "cw_r1cs_products.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
 
@@ -1687,6 +1688,25 @@ extern "C" int cw_r1cs_stream_plan(const cw_circuit *c, uint32_t terms_per_chunk
     return CW_OK;
 }
 
+// host-only: the plan of cw_get_r1cs_products in file order (cw_r1cs_products.h), for comparing it with the constraint system on
+// the CPU (tests/test_r1cs_products.py).  bits != 0: the plan of a bit-plane batch run by the interpreter (its signal map).
+extern "C" int cw_r1cs_products_plan(const cw_circuit *c, uint32_t bits, uint64_t sizes[4], uint32_t *rowptr, uint32_t *terms, uint32_t *ctab) {
+    if (!c || !sizes) return fail(CW_EINVAL, "null argument");
+    if (c->n_constraints == 0) return fail(CW_ESTATE, "no .r1cs was loaded for this circuit");
+    if (bits && (c->is64 || !c->has_bits)) return fail(CW_ESTATE, "cw_r1cs_products_plan: the circuit has no bit-plane program");
+    const cwprod::Plan p = c->is64 ? cwprod::build64(c->r1_terms64, c->n_constraints)
+                                   : cwprod::build(c->r_ptr, c->r_slot, bits ? c->r_cc : c->r_coef, c->r_orig, bits ? &c->bits.sig_slot : nullptr);
+    if (p.rowptr.size() != (size_t)3 * c->n_constraints + 1)
+        return fail(CW_ESTATE, "cw_r1cs_products_plan: the term lists of the constraint system do not add up");
+    const std::vector<uint32_t> none, &tab = c->is64 ? none : bits ? c->r_cctab : c->r_ctab;
+    const uint64_t v[4] = {p.rowptr.size(), p.terms.size(), tab.size(), p.words};
+    memcpy(sizes, v, sizeof v);
+    if (rowptr) memcpy(rowptr, p.rowptr.data(), p.rowptr.size() * 4);
+    if (terms && !p.terms.empty()) memcpy(terms, p.terms.data(), p.terms.size() * 4);
+    if (ctab && !tab.empty()) memcpy(ctab, tab.data(), tab.size() * 4);
+    return CW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // batch
 // ---------------------------------------------------------------------------------------------------------
@@ -1719,6 +1739,10 @@ struct cw_batch {
     // R1CS check plan (cw_r1cs_plan.h) on the device; r1_entries != 0 selects the LDS-staged kernel
     DevBuf<uint32_t> d_rctab, d_rctab29, d_pchunk, d_prec, d_pterms, d_prow;
     uint32_t r1_chunks = 0, r1_entries = 0;
+    // cw_get_r1cs_products: the plan in file order (cw_r1cs_products.h) and, for a bit table, the canonical coefficients; made
+    // by the first call, a batch that never asks holds nothing
+    DevBuf<uint32_t> d_qrowptr, d_qterms, d_qcctab;
+    bool q_ready = false;
     DevBuf<void> d_in;             // AoS staging [batch][n_in][32]
     DevBuf<void> d_pmask;          // cw_set_inputs_bits: the caller's packed masks on the device (8 bytes per input and group)
     DevBuf<void> d_gather;         // [n_witness][32]
@@ -3457,6 +3481,92 @@ extern "C" int cw_get_witness_rows(cw_batch *b, uint32_t entry0, uint32_t n, uin
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     return CW_OK;
+}
+
+// ---- R1CS products out (cw_r1cs_products.h) ----
+// A.w, B.w, C.w of the constraints [row0, row0 + n_rows) for the instances [first, first + count): what every check kernel forms
+// and throws away.  The plan in FILE order is made and uploaded by the batch's first call (the stream is drained once: the plan
+// is a local) and freed with the batch.
+static int products_plan(cw_batch *b) {
+    if (b->q_ready) return CW_OK;
+    const cw_circuit *c = b->c;
+    const cwprod::Plan p = c->is64 ? cwprod::build64(c->r1_terms64, c->n_constraints)
+                                   : cwprod::build(c->r_ptr, c->r_slot, b->bitmode ? c->r_cc : c->r_coef, c->r_orig,
+                                                   b->bitmode ? b->bits_sigslot : nullptr);
+    if (p.rowptr.size() != (size_t)3 * c->n_constraints + 1)
+        return fail(CW_ESTATE, "cw_get_r1cs_products: the term lists of the constraint system do not add up");
+    HIPCHK(upload(&b->d_qrowptr, p.rowptr, b->stream));
+    HIPCHK(upload(&b->d_qterms, p.terms, b->stream));
+    if (b->bitmode) HIPCHK(upload(&b->d_qcctab, c->r_cctab, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->q_ready = true;
+    return CW_OK;
+}
+// one kernel per table layout (cw_kernels.h), walking the engines as rows_egress does:
+//   64-bit runtime     cw64_products_kernel - also in the supplied-witness state
+//   bit-plane batches  cw_bits_products_kernel on the table's masks; the instances the side batch re-ran are written over from
+//                      there, one launch per run of consecutive instances, and a side batch that holds the whole batch serves the
+//                      range alone.  The first egress after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_products_kernel with the check's coefficient tables
+static int products_egress(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, void *d_out) {
+    const cw_circuit *c = b->c;
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return products_egress(b->fb, parts, row0, n_rows, first, count, d_out);
+    }
+    if (int rc = products_plan(b)) return rc;
+    if (c->is64) {
+        HIPCHK(cwk64_products(b->stream, b->d_V64, b->d_qrowptr, b->d_qterms, parts, row0, n_rows, b->Bp, first, count, d_out));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        HIPCHK(cwk_bits_products(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_qrowptr, b->d_qterms, b->d_qcctab, parts, row0, n_rows, first,
+                                 count, d_out, c->P));
+        const size_t inst = cwprod::instance_bytes(parts, n_rows, 32);
+        return cw_rerun_runs(b->fb_inst, first, count, [&](uint32_t pos, uint32_t len, uint32_t off) {
+            return products_egress(b->fb, parts, row0, n_rows, pos, len, (char *)d_out + (size_t)off * inst);
+        });
+    }
+    HIPCHK(cwk_products(b->stream, b->d_V, b->d_qrowptr, b->d_qterms, b->d_rctab, b->d_rctab29, parts, row0, n_rows, b->Bp, first, count, d_out,
+                        c->mont, c->P));
+    return CW_OK;
+}
+// what both calls check first, in the order of the other getters: null / parts / ranges / alignment (CW_EINVAL), the device, the state
+static int products_ready(cw_batch *b, const void *out, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count,
+                          bool device) {
+    if (!b || !out) return fail(CW_EINVAL, "null argument");
+    const char *who = device ? "cw_get_r1cs_products_device" : "cw_get_r1cs_products";
+    const char *why = cwprod::check_range(parts, row0, n_rows, b->c->n_constraints, first, count, b->batch);
+    if (!why && device) why = cwprod::check_device(out, cw_element_bytes(b->c));
+    if (why) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    NEED_DEVICE(b);
+    if (!b->ran) return fail(CW_ESTATE, std::string(who) + " before cw_run");
+    if (b->supplied && b->wit_missing)
+        return fail(CW_ESTATE, std::string(who) + ": witnesses missing for " + std::to_string(b->wit_missing) + " instances");
+    HIPCHK(hipSetDevice(b->device));
+    return CW_OK;
+}
+extern "C" int cw_get_r1cs_products_device(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count,
+                                           void *d_out) {
+    if (int rc = products_ready(b, d_out, parts, row0, n_rows, first, count, true)) return rc;
+    if (n_rows == 0 || count == 0) return CW_OK;
+    return products_egress(b, parts, row0, n_rows, first, count, d_out);
+}
+// Host image: pieces of whole instances are staged in d_bulk (cw_pieces / piece_rows, as get_witnesses_host does) and copied to
+// their place in the caller's image, which has the same layout.  Synchronised before the staging buffer is written again and
+// before returning.
+extern "C" int cw_get_r1cs_products(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, uint8_t *out) {
+    if (int rc = products_ready(b, out, parts, row0, n_rows, first, count, false)) return rc;
+    if (n_rows == 0 || count == 0) return CW_OK;
+    const size_t inst = cwprod::instance_bytes(parts, n_rows, cw_element_bytes(b->c));
+    const uint32_t per = piece_rows(inst, count);
+    HIPCHK(b->d_bulk.grow((size_t)per * inst));
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t m) {
+        if (int rc = products_egress(b, parts, row0, n_rows, first + done, m, b->d_bulk)) return rc;
+        HIPCHK(hipMemcpyAsync(cwprod::piece_at(out, inst, done), b->d_bulk, cwprod::piece_bytes(inst, m), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return CW_OK;
+    });
 }
 
 extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]) {

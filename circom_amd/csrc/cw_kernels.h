@@ -70,6 +70,19 @@ hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, ui
                            uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word);
 hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
                          uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word, bool mont, const FpParams &P);
+// R1CS products OUT (cw_get_r1cs_products*, cw_r1cs_products.h), one kernel per table layout: d_out[j][p][k] = the p-th part of
+// `parts` (bits 0 / 1 / 2 = A / B / C, in that order) of constraint row0 + k of the .r1cs file in instance first + j, canonical
+// residues of 32 bytes (d_out 16-byte aligned) or, 64-bit runtime, 8 bytes (8-byte aligned); dense, count x popcount(parts) x
+// n_rows elements.  rowptr / terms: the plan in file order ({slot, coefficient id} / {bit-table slot, id into cctab} / {slot, 0,
+// coefficient lo, hi}); ctab / ctab29: the check's coefficient tables.
+hipError_t cwk_products(hipStream_t s, const void *V, const uint32_t *rowptr, const uint32_t *terms, const uint32_t *ctab, const uint32_t *ctab29,
+                        uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t Bp, uint32_t first, uint32_t count, void *d_out, bool mont,
+                        const FpParams &P);
+hipError_t cwk_bits_products(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *rowptr, const uint32_t *terms,
+                             const uint32_t *cctab, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, void *d_out,
+                             const FpParams &P);
+hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, const void *terms, uint32_t parts, uint32_t row0, uint32_t n_rows,
+                          uint32_t Bp, uint32_t first, uint32_t count, void *d_out);
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,
                          uint32_t n_ichunks, const uint32_t *iterms, const uint32_t *itab, const uint32_t *irow_orig, const void *T,

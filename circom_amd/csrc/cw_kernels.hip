@@ -10,6 +10,7 @@
 #include "cw_kernels.h"
 #include "fp256.hip.h"
 #include "cw_rowops.hip.h"
+#include "cw_r1cs_products.h"
 
 #define CW_BLOCK 256
 
@@ -1096,6 +1097,72 @@ cw_pack_rows_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * 65 + lane];
 }
 
+// ---- R1CS products (cw_get_r1cs_products*) ------------------------------------------------------------------
+// out[j][p][k] (32 bytes, canonical) = the part's sum of coefficient * w[wire] over the terms of constraint row0 + k in instance
+// first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order: rowptr[3 row + part]
+// .. rowptr[3 row + part + 1] into terms {slot, coefficient id}; the ids are what r1_term reads: 0 / 1 = add / subtract the wire,
+// bit 31 = the constant wire, whose ctab entry is added as it stands (the table's form of the coefficient; on a canonical table
+// it is the file's number, which may be >= q: reduced here), otherwise the product with ctab29 (c R' as 9 x 29-bit limbs).  A
+// workgroup of four waves owns 64 instances (blockIdx.x) x PR_TILE constraints (blockIdx.y), the tile of cw_gather_many_kernel:
+//   sum     lane = instance, wave w takes the rows w, w + 4, ...; a term is a scalar load of 8 bytes and the two 1 KiB reads of
+//           v_load.  MONT: the sum leaves Montgomery form by ONE product with 1.  An empty part is 0.
+//   stage   tile[row][half][instance] (+1: bank spread).  One part after the other: the terms of A, B and C are disjoint runs,
+//           nothing is walked twice, the tile is reused (a barrier on either side of the stores).
+//   write   32 consecutive 16-byte pieces = PR_TILE rows of ONE instance and part, 512 contiguous bytes; a store instruction of
+//           a wave writes two such runs.
+// `out` points at the launch's first row in instance `first`'s image; `image_rows` = rows of the whole call, n_sel = selected
+// parts.  Instances past `count` and rows past n_rows are neither read nor written.
+#define PR_TILE 16
+template <bool MONT>
+__global__ void __launch_bounds__(256)
+cw_products_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ rowptr, const uint2 *__restrict__ terms,
+                   const uint32_t *__restrict__ ctab, const uint32_t *__restrict__ ctab29, uint32_t parts, uint32_t n_sel, uint32_t row0,
+                   uint32_t n_rows, uint32_t image_rows, uint32_t Bp, uint32_t first, uint32_t count, uint4 *__restrict__ out, FpParams P) {
+    __shared__ uint4 tile[PR_TILE][2][65];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t j0 = blockIdx.x * 64u, k0 = blockIdx.y * PR_TILE;
+    const uint32_t nk = n_rows - k0 < PR_TILE ? n_rows - k0 : PR_TILE, nj = count - j0 < 64u ? count - j0 : 64u;
+    const uint32_t i = first + j0 + (lane < nj ? lane : 0u);
+    constexpr uint32_t PIECES = 2 * PR_TILE, PER = 64 / PIECES;
+    const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
+    uint4 *o = out + ((size_t)j0 * n_sel * image_rows + k0) * 2 + piece;
+    uint32_t sel = 0;
+    for (uint32_t part = 0; part < 3; part++) {
+        if (!((parts >> part) & 1u)) continue;
+        for (uint32_t k = wave; k < nk; k += 4) {
+            const uint32_t *rp = rowptr + (size_t)(row0 + k0 + k) * 3 + part;
+            const uint32_t t1 = rp[1];
+            fe acc = fe_zero();
+            for (uint32_t t = rp[0]; t < t1; t++) {
+                const uint2 x = terms[t];
+                const uint32_t ci = x.y;
+                fe w;
+                if (ci >> 31) {
+                    w = c_load(ctab, ci & 0x7FFFFFFFu);
+                    if (!MONT)
+                        for (int it = 0; it < 64 && !fe_ltu(w, P.q); it++) w = fe_csub_q(w, P);
+                } else {
+                    w = v_load(V, x.x, Bp, i);
+                    if (ci >= 2) {
+                        fe29 cc;
+                        FE_UNROLL for (int q = 0; q < 9; q++) cc.l[q] = ctab29[(size_t)ci * 9 + q];
+                        w = fe_from29(fe29_mmul(fe_to29(w), cc, P));
+                    }
+                }
+                acc = (ci == 1) ? fe_sub(acc, w, P) : fe_add(acc, w, P);
+            }
+            if (MONT) acc = fe_mmul(acc, fe_small(1), P);
+            tile[k][0][lane] = make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+            tile[k][1][lane] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+        }
+        __syncthreads();
+        if (e < nk)
+            for (uint32_t ii = wave * PER + sub; ii < nj; ii += 4 * PER) o[((size_t)ii * n_sel + sel) * image_rows * 2] = tile[e][h][ii];
+        __syncthreads();
+        sel++;
+    }
+}
+
 // ---- Fp multiplication micro-benchmark: iters dependent Montgomery products per lane --------------------
 __global__ void __launch_bounds__(CW_BLOCK)
 cw_mulbench_kernel(const uint4 *__restrict__ a, const uint4 *__restrict__ b, uint4 *__restrict__ out, uint32_t n,
@@ -1375,4 +1442,22 @@ hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint4 *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8, d_word,
                        one_lo, one_hi);
     return hipGetLastError();
+}
+// R1CS products [count][n_sel][n_rows] of 32-byte canonical residues from the 8 x u32 table: instance tiles in gridDim.x, row tiles
+// of PR_TILE in gridDim.y, a range of more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one
+// that failed
+static_assert(PR_TILE == cwprod::ROWS256, "the row tile of cw_products_kernel");
+hipError_t cwk_products(hipStream_t s, const void *V, const uint32_t *rowptr, const uint32_t *terms, const uint32_t *ctab, const uint32_t *ctab29,
+                        uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t Bp, uint32_t first, uint32_t count, void *d_out, bool mont,
+                        const FpParams &P) {
+    const uint32_t n_sel = cwprod::n_parts(parts);
+    if (n_rows == 0 || count == 0) return hipSuccess;
+    if (n_sel == 0 || (parts & ~cwprod::PART_ALL) || ((uintptr_t)d_out & 15)) return hipErrorInvalidValue;
+    const auto kernel = mont ? cw_products_kernel<true> : cw_products_kernel<false>;
+    return cwprod::row_pieces(n_rows, PR_TILE, [&](uint32_t off, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((count >> 6) + ((count & 63u) != 0), cwprod::row_tiles(m, PR_TILE)), dim3(256), 0, s, (const uint4 *)V,
+                           rowptr, (const uint2 *)terms, ctab, ctab29, parts, n_sel, row0 + off, m, n_rows, Bp, first, count,
+                           (uint4 *)d_out + (size_t)off * 2, P);
+        return hipGetLastError();
+    });
 }

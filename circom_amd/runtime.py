@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ["CW_LIB"]).resolve() if os.environ.get("CW_LIB") else
 
 ST_OK, ST_ASSERT_FAILED, ST_ARITH, ST_R1CS_FAILED, ST_BAD_WITNESS = 0, 1, 2, 4, 8
 ROWS_MSB_FIRST = 1      # CW_ROWS_MSB_FIRST
+R1CS_A, R1CS_B, R1CS_C = 1, 2, 4     # CW_R1CS_A / _B / _C: the parts of cw_get_r1cs_products
 
 
 class CwError(RuntimeError):
@@ -113,6 +114,8 @@ _SIGS = {
     "cw_get_signal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "cw_get_r1cs_first_bad": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cw_get_r1cs_products": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_get_r1cs_products_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_write_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtnsb": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cw_set_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -127,6 +130,7 @@ _SIGS = {
     "cw_get_log": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t]),
     "cw_r1cs_plan_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_r1cs_stream_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_r1cs_products_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_device_values": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "cw_fp_mul_bench": (C.c_int, [C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_float)]),
@@ -224,6 +228,15 @@ class Circuit:
         _chk(lib().cw_r1cs_plan_stats(self.h, batch, chunks, entries, out))
         keys = ("chunks", "loads", "terms", "filler_loads", "distinct_wires", "entries", "depth")
         return dict(zip(keys, [int(x) for x in out]))
+
+    def r1cs_products_plan(self, bits: bool = False) -> dict:
+        """The plan Batch.r1cs_products walks, in the order of the .r1cs file (host only; csrc/cw_r1cs_products.h):
+        rowptr [3 n + 1], terms [n_terms][2] ({slot, coefficient id}; 64-bit runtime: [n_terms][4] {slot, 0, lo, hi}), ctab [ids][8]"""
+        sizes = (C.c_uint64 * 4)()
+        _chk(lib().cw_r1cs_products_plan(self.h, 1 if bits else 0, sizes, None, None, None))
+        arrs = [np.zeros(int(sizes[k]), dtype=np.uint32) for k in range(3)]
+        _chk(lib().cw_r1cs_products_plan(self.h, 1 if bits else 0, sizes, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+        return {"rowptr": arrs[0], "terms": arrs[1].reshape(-1, int(sizes[3])), "ctab": arrs[2].reshape(-1, 8)}
 
     def r1cs_stream_plan(self, terms_per_chunk: int = 192, no_bool: bool = False, no_fold: bool = False) -> dict:
         """The term stream of the default R1CS check kernel, as the batch uploads it (host only; csrc/cw_r1cs_plan.h)."""
@@ -431,6 +444,25 @@ class Batch:
         out = np.zeros(self.n, dtype=np.uint32)
         _chk(lib().cw_get_r1cs_first_bad(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def r1cs_products(self, parts: int = R1CS_A | R1CS_B, row0: int = 0, n_rows: int | None = None, first: int = 0,
+                      count: int | None = None) -> np.ndarray:
+        """A.w, B.w, C.w of the constraints [row0, row0 + n_rows) of the .r1cs file for the instances [first, first + count), every
+        engine (cw_get_r1cs_products): uint8 [count][P][n_rows][element_bytes], P = the parts of `parts` (R1CS_A | R1CS_B | R1CS_C)
+        in the order A, B, C, canonical little-endian residues"""
+        n_rows = self.circuit.n_constraints - row0 if n_rows is None else n_rows
+        count = self.n - first if count is None else count
+        n_sel = bin(parts & 7).count("1")
+        out = np.zeros((max(count, 0), n_sel, max(n_rows, 0), self.circuit.element_bytes), dtype=np.uint8)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the ranges)
+        ptr = out.ctypes.data_as(C.c_void_p) if out.size else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _chk(lib().cw_get_r1cs_products(self.h, parts, row0, n_rows, first, count, ptr))
+        return out
+
+    def r1cs_products_device(self, parts: int, row0: int, n_rows: int, first: int, count: int, d_ptr: int) -> None:
+        """the same into device memory: [count][P][n_rows][element_bytes] at d_ptr, aligned to 8 bytes (64-bit runtime) or 16;
+        asynchronous on the batch's stream (cw_get_r1cs_products_device)"""
+        _chk(lib().cw_get_r1cs_products_device(self.h, parts, row0, n_rows, first, count, C.c_void_p(d_ptr)))
 
     def witness_bytes(self, instance: int) -> bytes:
         out = np.zeros(self.circuit.n_witness * 32, dtype=np.uint8)

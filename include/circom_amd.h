@@ -354,6 +354,41 @@ uint32_t cw_n_log_statements(const cw_circuit *c);
 int64_t cw_get_log(cw_batch *b, uint32_t instance, char *out, size_t out_len);
 /* first violated constraint per instance after cw_check_r1cs: [batch], 0xFFFFFFFF = none */
 int cw_get_r1cs_first_bad(cw_batch *b, uint32_t *row);
+/* R1CS products OUT, every engine: the three linear forms A.w, B.w, C.w of every constraint - what a Groth16 prover builds first
+ * (A.w and B.w over all constraints, then C.w = A.w o B.w and the NTT), what a Spartan / Nova style prover needs all of, and what
+ * shows on which side a violated row is off.  Every check kernel forms them and throws them away; here they leave the device
+ * without the witness leaving it first.
+ *   image        out[j][p][k]: instance first + j; the p-th selected part of `parts` (CW_R1CS_A | CW_R1CS_B | CW_R1CS_C) in the
+ *                order A, B, C; constraint row0 + k in the order of the .r1cs file - the numbering of cw_get_r1cs_first_bad and
+ *                cw_explain.  Dense: count x popcount(parts) x n_rows elements, offsets in 64-bit arithmetic.
+ *   element      cw_element_bytes(c) bytes (8 for the 64-bit runtime, 32 otherwise): the canonical little-endian residue < q.  A
+ *                table of Montgomery forms is converted on the way out, as every other egress does.
+ *   value        the sum of coefficient x w[wire] over the terms of that part of that row as the .r1cs given to cw_load states
+ *                them: an empty part is 0, a term on wire 0 is its coefficient, a coefficient >= q (where the loader accepts
+ *                one) counts reduced.  The full system is used whatever cw_set_witness_list says: the list shortens egress.
+ *   errors       in the order of the other getters: a null batch or pointer; parts == 0 or a bit outside 7; row0 + n_rows >
+ *                cw_n_constraints or first + count > batch (no 32-bit wrap); device form: d_out not aligned to 8 bytes (64-bit
+ *                runtime) or 16 bytes (the pointer is not touched): CW_EINVAL.  Then the device (a host-only batch: CW_EDEVICE),
+ *                then the state: CW_ESTATE "... before cw_run" for a batch that has neither run nor been supplied, "witnesses
+ *                missing for N instances" for a supplied table with gaps, as cw_check_r1cs answers.
+ *   empty        n_rows == 0 or count == 0: CW_OK, nothing is written.
+ *   lifetime     the host form copies in pieces through a staging buffer and synchronises before it returns.  The device form
+ *                is asynchronous on the batch's stream - with the one exception of every device egress: the first one after a
+ *                cw_run of a bit-plane batch waits for the evaluation.  The call only reads the table: status words, first-bad
+ *                rows, a captured cw_run_check graph and the supplied state stay as they were; before or after cw_check_r1cs.
+ *   memory       the plan (row pointers in file order, plain term lists: csrc/cw_r1cs_products.h) goes to the device with the
+ *                batch's FIRST call, which drains the stream once, and is freed with the batch; a batch that never asks pays
+ *                nothing.
+ *   engines      64-bit runtime (csrc/cw64.hip cw64_products_kernel, also in the supplied-witness state), 256-bit schedule
+ *                (csrc/cw_kernels.hip cw_products_kernel, canonical and Montgomery-form tables), bit-plane batches
+ *                (csrc/cw_bits.hip cw_bits_products_kernel, both table layouts: a select per term, no multiplication; the
+ *                instances the 256-bit side batch re-ran are written over from there).  Lane = instance, the tile turned
+ *                through LDS: every store is 512 contiguous bytes of one instance's run of rows. */
+#define CW_R1CS_A 1u
+#define CW_R1CS_B 2u
+#define CW_R1CS_C 4u
+int cw_get_r1cs_products(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, uint8_t *out);
+int cw_get_r1cs_products_device(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, void *d_out);
 /* host-only: build and hazard-check the LDS staging plan of the R1CS check kernel for `chunks` row chunks
    and `entries` 2-KiB LDS entries per wave (0 = the defaults cw_batch_create would pick for `batch`).
    out[8] = {chunks, loads, terms, filler loads, distinct wires, entries, prefetch depth, 0}. */
@@ -365,6 +400,14 @@ int cw_r1cs_plan_stats(const cw_circuit *c, uint32_t batch, uint32_t chunks, uin
    written (call once for the sizes).  No reference counterpart (snarkjs `wtns check` is the reference-side check). */
 int cw_r1cs_stream_plan(const cw_circuit *c, uint32_t terms_per_chunk, uint32_t flags, uint64_t sizes[8], uint32_t *chunk,
                         uint32_t *terms, uint32_t *row_orig, uint32_t *ctab);
+/* host-only: the plan cw_get_r1cs_products walks (csrc/cw_r1cs_products.h), so that a test can compare it with the constraint
+   system on the CPU: rowptr[3 n + 1] in the order of the .r1cs file (constraint k, part p: the terms rowptr[3 k + p] ..
+   rowptr[3 k + p + 1]) into terms of sizes[3] words: {slot, coefficient id into ctab as cw_r1cs_stream_plan hands it out: 0 = +1,
+   1 = -1, bit 31 = the constant wire, entry taken as it stands, else c * 2^261 mod q}; bits != 0: the plan of a bit-plane batch,
+   {bit-table slot of the interpreter's table, id of the canonical coefficient in ctab}; 64-bit runtime: {slot, 0, coefficient
+   lo, hi}, no ctab.  sizes[4] = {words of rowptr[], words of terms[], words of ctab[], words per term}; a null buffer is not
+   written (call once for the sizes). */
+int cw_r1cs_products_plan(const cw_circuit *c, uint32_t bits, uint64_t sizes[4], uint32_t *rowptr, uint32_t *terms, uint32_t *ctab);
 
 /* raw device pointers for zero-copy consumers (provers): value table, layout in DESIGN.md.  When cw_circuit_montgomery()
    is 1 the table holds x * 2^261 mod q (the schedule of an arithmetic circuit keeps its signals in Montgomery form, so that
