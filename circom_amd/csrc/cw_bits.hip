@@ -475,6 +475,101 @@ cw_bits_gather_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t l
     }
 }
 
+// Egress by index (cw_get_witnesses_at*): out[j][k] (32 bytes) = witness element k of the range in instance idx[j].  The tile
+// and the stores of the kernel above - a wave owns 32 * BITS_GATHER_RUN elements x 64 list positions and writes whole 1 KiB runs
+// of one position, even lanes carrying the bit -, but the 64 positions of a tile may lie in 64 different groups, so there is no
+// window to read: the wave FORMS the 64-bit window of an element.  Lane l holds position j0 + l: its instance (loaded once, before
+// the loop over the elements), the address of its group (bits_group: both table layouts) and its bit number.  Per element the
+// slot is a scalar load (wslot[k], wave-uniform), every lane reads ITS group's word of that slot and a ballot of the lanes' bits
+// is the window, bit l = the value at position j0 + l; it is kept by the two lanes that write the element.  For an ascending
+// dense list the 64 words of a read are one or two distinct addresses.  No LDS.
+//   dense   a tile whose live positions are all valid and name CONSECUTIVE instances (one ballot decides; what the tiles of an
+//           ascending dense list mostly are, the identity list always) has a window to read after all: the kernel above's read -
+//           one mask per lane pair from the group of the first instance, shifted, the next group's OR-ed in when the run crosses
+//           into it - 8 loads per wave instead of 256 scalar loads, 256 vector loads and 256 ballots.
+//   grid    as above: with 8 or more tiles of positions per launch the grid walks the positions fastest (`tiles_fastest`).
+//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list; with d_n the list ends
+//           at min(count, *d_n - pos0), read here; a wave whose tile lies behind it leaves at once, rows behind it are not written.
+//   bad     a position whose index is >= batch reads nothing and contributes 0 to every ballot: its row is zeros.  One lane of
+//           the tile's first wave reports the lowest such position, pos0 + j0 + l, with atomicMin (`bad` may be nullptr; the
+//           caller fills it first).
+// The rows of the instances the side batch re-ran are written over afterwards (cw_kernels.hip cw_gather_at_kernel with the
+// instance -> side-batch map), in stream order.
+__global__ void __launch_bounds__(256)
+cw_bits_gather_at_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n_wit,
+                         uint32_t batch, const uint32_t *__restrict__ idx, uint32_t count, uint32_t pos0, const uint32_t *__restrict__ d_n,
+                         uint4 *__restrict__ out, uint32_t *bad, uint32_t tiles_fastest) {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t bk = tiles_fastest ? blockIdx.y : blockIdx.x, bj = tiles_fastest ? blockIdx.x : blockIdx.y;
+    const uint32_t k0 = (bk * 4 + wv) * 32 * BITS_GATHER_RUN;               // this wave's elements
+    const uint32_t j0 = bj * 64;                                             // its 64 list positions
+    uint32_t lim = count;
+    if (d_n) {
+        const uint32_t dn = *d_n, left = dn > pos0 ? dn - pos0 : 0u;
+        lim = left < lim ? left : lim;
+    }
+    if (k0 >= n_wit || j0 >= lim) return;
+    const uint32_t nj = min(64u, lim - j0);
+    const uint32_t inst = lane < nj ? idx[j0 + lane] : 0u;
+    const bool ok = lane < nj && inst < batch;
+    const uint64_t off = __ballot(lane < nj && !ok);
+    if (bad && off && k0 == 0 && lane == 0) atomicMin(bad, pos0 + j0 + (uint32_t)__builtin_ctzll(off));
+    const uint64_t *Tg = bits_group(T, slots, lsh, ok ? inst >> 6 : 0u);
+    const uint32_t bit_no = inst & 63u;
+    uint64_t win[BITS_GATHER_RUN];                                           // bit jj = the value at position j0 + jj
+    bool have[BITS_GATHER_RUN];
+    const uint32_t inst0 = __builtin_amdgcn_readfirstlane(inst);            // position j0 is always live
+    const bool dense = __ballot(lane < nj && (!ok || inst != inst0 + lane)) == 0;
+    if (dense) {
+        // instances inst0 .. inst0 + nj - 1, all < batch: the run crosses into group g + 1 when 64 - sh < nj, and that group exists
+        const uint32_t g = inst0 >> 6, sh = inst0 & 63u;
+        const bool two = sh && 64u - sh < nj;
+#pragma unroll
+        for (int r = 0; r < BITS_GATHER_RUN; r++) {
+            const uint32_t k = k0 + r * 32 + (lane >> 1);
+            have[r] = k < n_wit;
+            win[r] = 0;
+            if (have[r]) {
+                const uint32_t sl = wslot[k];
+                win[r] = bits_group(T, slots, lsh, g)[(size_t)sl << lsh] >> sh;
+                if (two) win[r] |= bits_group(T, slots, lsh, g + 1)[(size_t)sl << lsh] << (64 - sh);
+            }
+        }
+    } else
+#pragma unroll
+    for (int r = 0; r < BITS_GATHER_RUN; r++) {
+        const uint32_t kr = k0 + r * 32;
+        have[r] = kr + (lane >> 1) < n_wit;
+        win[r] = 0;
+        // eight elements at a time: eight slots and eight words in flight before the first ballot.  An element past n_wit takes
+        // the slot of the run's first element (always an entry of the list); its window is kept by no lane that writes
+        for (uint32_t k8 = 0; k8 < 32 && kr + k8 < n_wit; k8 += 8) {
+            uint64_t word[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8; u++) {
+                const uint32_t k = kr + k8 + u;
+                const uint32_t sl = wslot[k < n_wit ? k : kr];               // wave-uniform
+                word[u] = ok ? Tg[(size_t)sl << lsh] : 0;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 8; u++) {
+                const uint64_t m = __ballot((word[u] >> bit_no) & 1);
+                if ((lane >> 1) == k8 + u) win[r] = m;
+            }
+        }
+    }
+    const bool low_half = !(lane & 1);
+    uint4 *o = out + ((size_t)j0 * n_wit + k0) * 2 + lane;
+    for (uint32_t jj = 0; jj < nj; jj++) {
+#pragma unroll
+        for (int r = 0; r < BITS_GATHER_RUN; r++) {
+            const uint32_t bit = low_half ? (uint32_t)(win[r] >> jj) & 1u : 0u;
+            if (have[r]) o[r * 64] = make_uint4(bit, 0u, 0u, 0u);
+        }
+        o += (size_t)n_wit * 2;
+    }
+}
+
 // packed main inputs (cw_set_inputs_bits*): masks[group][k] -> bit-table slot input_slot0 + k
 __global__ void __launch_bounds__(256)
 cw_bits_ingest_packed_kernel(const uint64_t *__restrict__ masks, uint64_t *__restrict__ T, uint64_t slots, uint32_t sh, uint32_t input_slot0,
@@ -960,6 +1055,22 @@ hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_
         const uint32_t gf = groups >= 8 && kblocks <= 65535u;           // see the kernel's comment
         hipLaunchKernelGGL(cw_bits_gather_kernel, gf ? dim3(groups, kblocks) : dim3(kblocks, groups), dim3(256), 0, s, (const uint64_t *)T, slots,
                            sh, wslot, n_wit, first + done, n, (uint4 *)out + (size_t)done * n_wit * 2, gf);
+        return hipGetLastError();
+    });
+}
+// egress by index from the bit table: element blocks in gridDim.x, tiles of 64 list positions in gridDim.y (65 535 per launch, a
+// longer list in several launches, none behind one that failed).  `bad` (or nullptr) takes an atomicMin of the lowest position
+// whose index is >= batch; the caller fills it first.
+hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t batch,
+                              const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t *d_bad) {
+    if (!n_idx || !n_wit) return hipSuccess;
+    if (((uintptr_t)d_out & 15) || (((uintptr_t)d_idx | (uintptr_t)d_n_idx | (uintptr_t)d_bad) & 3)) return hipErrorInvalidValue;
+    const uint32_t kblocks = (n_wit + 128 * BITS_GATHER_RUN - 1) / (128 * BITS_GATHER_RUN);
+    return cw_pieces(n_idx, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        const uint32_t tiles = (m + 63) / 64;
+        const uint32_t tf = tiles >= 8 && kblocks <= 65535u;            // see cw_bits_gather_kernel's comment
+        hipLaunchKernelGGL(cw_bits_gather_at_kernel, tf ? dim3(tiles, kblocks) : dim3(kblocks, tiles), dim3(256), 0, s, (const uint64_t *)T, slots,
+                           sh, wslot, n_wit, batch, d_idx + done, m, done, d_n_idx, (uint4 *)d_out + (size_t)done * n_wit * 2, d_bad, tf);
         return hipGetLastError();
     });
 }

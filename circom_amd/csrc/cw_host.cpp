@@ -24,6 +24,7 @@
 #include "cw_pieces.h"
 #include "cw_rows.h"
 #include "cw_r1cs_products.h"
+#include "cw_select.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
 
@@ -1743,6 +1744,12 @@ struct cw_batch {
     // by the first call, a batch that never asks holds nothing
     DevBuf<uint32_t> d_qrowptr, d_qterms, d_qcctab;
     bool q_ready = false;
+    // instance lists (cw_select_instances*, cw_get_witnesses_at*; cw_select.h): the block counts of the select kernels, the list of
+    // the host forms, and, for a bit-plane batch, fb_index on the device - uploaded by the first select or indexed egress after a
+    // resolve (fbmap_ready) and freed with the batch; a batch that never asks holds nothing
+    DevBuf<uint32_t> d_selcnt, d_selidx;
+    DevBuf<int32_t> d_fbindex;
+    bool fbmap_ready = false;
     DevBuf<void> d_in;             // AoS staging [batch][n_in][32]
     DevBuf<void> d_pmask;          // cw_set_inputs_bits: the caller's packed masks on the device (8 bytes per input and group)
     DevBuf<void> d_gather;         // [n_witness][32]
@@ -2871,6 +2878,7 @@ static int bits_run(cw_batch *b, const void *in) {
     }
     TMARK(b, 2);
     b->resolved = false;
+    b->fbmap_ready = false;
     b->checked = false;
     return CW_OK;
 }
@@ -3216,6 +3224,7 @@ extern "C" int cw_run_check(cw_batch *b) {
     if (b->bitmode) {
         if (b->jit) b->table_dirty = false;
         b->resolved = false;
+        b->fbmap_ready = false;
         b->checked = true;
     }
     return CW_OK;
@@ -3481,6 +3490,155 @@ extern "C" int cw_get_witness_rows(cw_batch *b, uint32_t entry0, uint32_t n, uin
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     return CW_OK;
+}
+
+// ---- instance lists: select by status on the device, egress by index (cw_select.h) ----
+// The state both halves check last, in the order of the other getters: a batch that has neither run nor been supplied, then a
+// supplied table with gaps - the text of cw_check_r1cs.
+static int list_state(cw_batch *b, const char *who) {
+    NEED_DEVICE(b);
+    if (!b->ran) return fail(CW_ESTATE, std::string(who) + " before cw_run");
+    if (b->supplied && b->wit_missing)
+        return fail(CW_ESTATE, std::string(who) + ": witnesses missing for " + std::to_string(b->wit_missing) + " instances");
+    HIPCHK(hipSetDevice(b->device));
+    return CW_OK;
+}
+// bit-plane batches: fb_index (instance -> position in the side batch, or -1) on the device, uploaded by the first call after a
+// resolve.  fb_index is a member and stays as it is until the next resolve, which drains the stream first.
+static int fb_map(cw_batch *b) {
+    if (b->fbmap_ready) return CW_OK;
+    HIPCHK(b->d_fbindex.grow((size_t)b->batch * 4));
+    HIPCHK(hipMemcpyAsync(b->d_fbindex, b->fb_index.data(), (size_t)b->batch * 4, hipMemcpyHostToDevice, b->stream));
+    b->fbmap_ready = true;
+    return CW_OK;
+}
+// d_idx[0 .. *d_n) = the instances whose status word - the word cw_get_status returns - matches; d_idx == nullptr: the count only.
+// Bit-plane batches wait for the evaluation once (bits_resolve) and judge a re-run instance by the side batch's word; a side
+// batch that holds the whole batch answers alone.  Asynchronous on the batch's stream.
+static int select_on_device(cw_batch *b, uint32_t mask, uint32_t want, uint32_t *d_idx, uint32_t *d_n) {
+    const int32_t *fbidx = nullptr;
+    const uint32_t *fbstatus = nullptr;
+    uint32_t n_fb = 0;
+    const cw_batch *src = b;
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) {
+            src = b->fb;                                                 // (its batch may be larger: the tail repeats an instance)
+        } else if (b->fb && !b->fb_inst.empty()) {
+            if (int rc = fb_map(b)) return rc;
+            fbidx = b->d_fbindex;
+            fbstatus = b->fb->d_status;
+            n_fb = (uint32_t)b->fb_inst.size();
+        }
+    }
+    HIPCHK(b->d_selcnt.grow((size_t)std::max<uint32_t>(cwsel::n_blocks(b->batch), 1) * 4));
+    HIPCHK(cwk_select(b->stream, src->d_status, b->batch, mask, want, fbidx, fbstatus, n_fb, b->d_selcnt, d_idx, d_n));
+    return CW_OK;
+}
+extern "C" int cw_select_instances_device(cw_batch *b, uint32_t mask, uint32_t want, void *d_idx, void *d_n) {
+    if (!b) return fail(CW_EINVAL, "null argument");
+    if (const char *why = cwsel::check_select_device(d_idx, d_n)) return fail(CW_EINVAL, std::string("cw_select_instances_device: ") + why);
+    if (int rc = list_state(b, "cw_select_instances_device")) return rc;
+    return select_on_device(b, mask, want, (uint32_t *)d_idx, (uint32_t *)d_n);
+}
+// The host form selects into the batch's own list (batch + 1 words: the count behind it), reads the count, then that many indices.
+extern "C" int cw_select_instances(cw_batch *b, uint32_t mask, uint32_t want, uint32_t *idx, uint32_t *n) {
+    if (!b || !n) return fail(CW_EINVAL, "null argument");
+    if (int rc = list_state(b, "cw_select_instances")) return rc;
+    HIPCHK(b->d_selidx.grow(((size_t)b->batch + 1) * 4));
+    uint32_t *d_n = b->d_selidx.get() + b->batch;
+    if (int rc = select_on_device(b, mask, want, idx ? b->d_selidx.get() : nullptr, d_n)) return rc;
+    uint32_t found = 0;
+    HIPCHK(hipMemcpyAsync(&found, d_n, 4, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (found > b->batch) return fail(CW_EDEVICE, "cw_select_instances: the device counted more instances than the batch holds");
+    if (idx && found) {
+        HIPCHK(hipMemcpyAsync(idx, b->d_selidx, (size_t)found * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    *n = found;
+    return CW_OK;
+}
+
+// Entries [skip, skip + n) of the witness list for the instances d_idx[0 .. min(n_idx, *d_n_idx)), [n_idx][n][eb] in DEVICE memory
+// at d_out, one kernel per table layout (cw_kernels.h), walking the engines as device_egress does:
+//   64-bit runtime     cw64_egress_at_kernel, both element sizes - also in the supplied-witness state
+//   bit-plane batches  cw_bits_gather_at_kernel on the bit table (it reports the bad positions), then ONE launch of
+//                      cw_gather_at_kernel on the side batch's table with the instance -> side-batch map writes over the rows of
+//                      the re-run instances - the host never learns the list; a side batch that holds the whole batch serves the
+//                      list alone.  The first egress after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_gather_at_kernel, canonical and Montgomery-form tables
+// `limit`: the instances an index may name - the batch's, also where a (possibly larger) side batch serves the list.
+static int at_egress(cw_batch *b, uint32_t limit, uint32_t skip, uint32_t n, const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx,
+                     void *d_out, uint32_t eb, uint32_t *d_bad) {
+    const cw_circuit *c = b->c;
+    if (c->is64) {
+        HIPCHK(cwk64_egress_at(b->stream, b->d_V64, b->d_w2s + skip, n, b->Bp, limit, d_idx, n_idx, d_n_idx, d_out, eb, d_bad));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return at_egress(b->fb, limit, skip, n, d_idx, n_idx, d_n_idx, d_out, eb, d_bad);
+        HIPCHK(cwk_bits_gather_at(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + skip, n, limit, d_idx, n_idx, d_n_idx, d_out, d_bad));
+        if (!b->fb || b->fb_inst.empty()) return CW_OK;
+        if (int rc = fb_map(b)) return rc;
+        HIPCHK(cwk_gather_at(b->stream, b->fb->d_V, b->fb->d_w2s + skip, n, b->fb->Bp, (uint32_t)b->fb_inst.size(), d_idx, n_idx, d_n_idx,
+                             b->d_fbindex, b->batch, d_out, nullptr, b->fb->c->mont, b->fb->c->P));
+        return CW_OK;
+    }
+    HIPCHK(cwk_gather_at(b->stream, b->d_V, b->d_w2s + skip, n, b->Bp, limit, d_idx, n_idx, d_n_idx, nullptr, 0, d_out, d_bad, c->mont, c->P));
+    return CW_OK;
+}
+static int witnesses_at_device(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx, void *d_out,
+                               void *d_bad, uint32_t eb, const char *who) {
+    if (!b) return fail(CW_EINVAL, "null argument");
+    const char *why = cwsel::check_at_device(d_idx, d_n_idx, d_out, d_bad, eb);
+    if (!why) why = cwsel::check_entries(entry0, n, b->c->n_witness);
+    if (why) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    if (int rc = list_state(b, who)) return rc;
+    if (d_bad) HIPCHK(cwk_fill32(b->stream, (uint32_t *)d_bad, cwsel::NONE, 1));
+    if (n == 0 || n_idx == 0) return CW_OK;
+    return at_egress(b, b->batch, entry0, n, (const uint32_t *)d_idx, n_idx, (const uint32_t *)d_n_idx, d_out, eb, (uint32_t *)d_bad);
+}
+// Host list, host image: the whole list is validated first; then pieces of whole rows go through the staging buffer (cw_pieces,
+// as get_witnesses_host does), the piece's indices uploaded behind its rows.  Synchronised before the staging buffer is written
+// again and before returning.
+static int witnesses_at_host(cw_batch *b, uint32_t entry0, uint32_t n, const uint32_t *idx, uint32_t n_idx, uint8_t *out, uint32_t eb,
+                             const char *who) {
+    if (!b || !idx || !out) return fail(CW_EINVAL, "null argument");
+    if (const char *why = cwsel::check_entries(entry0, n, b->c->n_witness)) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    const int64_t bad = cwsel::first_bad_position(idx, n_idx, b->batch);
+    if (bad >= 0)
+        return fail(CW_EINVAL, std::string(who) + ": idx[" + std::to_string(bad) + "] = " + std::to_string(idx[bad]) + " is not an instance of the batch");
+    if (int rc = list_state(b, who)) return rc;
+    if (n == 0 || n_idx == 0) return CW_OK;
+    const size_t row = (size_t)n * eb;
+    const uint32_t per = cwsel::piece_rows(row, n_idx);
+    HIPCHK(b->d_bulk.grow(cwsel::staging_bytes(row, per)));
+    uint32_t *d_list = (uint32_t *)((char *)b->d_bulk.get() + (size_t)per * row);
+    return cw_pieces(n_idx, per, [&](uint32_t done, uint32_t m) {
+        HIPCHK(hipMemcpyAsync(d_list, idx + done, (size_t)m * 4, hipMemcpyHostToDevice, b->stream));
+        if (int rc = at_egress(b, b->batch, entry0, n, d_list, m, nullptr, b->d_bulk, eb, nullptr)) return rc;
+        HIPCHK(hipMemcpyAsync(cwsel::piece_at(out, row, done), b->d_bulk, cwsel::piece_bytes(row, m), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return CW_OK;
+    });
+}
+extern "C" int cw_get_witnesses_at(cw_batch *b, uint32_t entry0, uint32_t n, const uint32_t *idx, uint32_t n_idx, uint8_t *out) {
+    return witnesses_at_host(b, entry0, n, idx, n_idx, out, 32, "cw_get_witnesses_at");
+}
+extern "C" int cw_get_witnesses_at_n8(cw_batch *b, uint32_t entry0, uint32_t n, const uint32_t *idx, uint32_t n_idx, uint8_t *out) {
+    if (b && !b->c->is64) return cw_get_witnesses_at(b, entry0, n, idx, n_idx, out);
+    return witnesses_at_host(b, entry0, n, idx, n_idx, out, 8, "cw_get_witnesses_at_n8");
+}
+extern "C" int cw_get_witnesses_at_device(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx,
+                                          void *d_out, void *d_bad) {
+    return witnesses_at_device(b, entry0, n, d_idx, n_idx, d_n_idx, d_out, d_bad, 32, "cw_get_witnesses_at_device");
+}
+extern "C" int cw_get_witnesses_at_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx,
+                                             void *d_out, void *d_bad) {
+    if (b && !b->c->is64) return cw_get_witnesses_at_device(b, entry0, n, d_idx, n_idx, d_n_idx, d_out, d_bad);
+    return witnesses_at_device(b, entry0, n, d_idx, n_idx, d_n_idx, d_out, d_bad, 8, "cw_get_witnesses_at_device_n8");
 }
 
 // ---- R1CS products out (cw_r1cs_products.h) ----

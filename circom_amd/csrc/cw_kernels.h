@@ -83,6 +83,26 @@ hipError_t cwk_bits_products(hipStream_t s, const void *T, uint64_t slots, uint3
                              const FpParams &P);
 hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, const void *terms, uint32_t parts, uint32_t row0, uint32_t n_rows,
                           uint32_t Bp, uint32_t first, uint32_t count, void *d_out);
+// instance lists (cw_select_instances*, cw_get_witnesses_at*, cw_select.h).
+//   cwk_select        d_idx[0 .. *d_n) = the instances i < batch with (w(i) & mask) == want, ascending; w(i) = status[i], or, with
+//                     fbidx (instance -> position in the side batch or negative) and fbidx[i] in [0, n_fb), fbstatus[fbidx[i]].
+//                     Three launches (count, scan, scatter; no workgroup waits for another); `counts`: scratch of
+//                     cwsel::n_blocks(batch) words; d_idx == nullptr: *d_n only.
+//   cwk*_at           one kernel per table layout: d_out[j][k] = entry k of the range (wslot / w2s point at its first entry) of
+//                     instance d_idx[j], j < min(n_idx, *d_n_idx) (d_n_idx may be nullptr), canonical, 32 bytes (d_out 16-byte
+//                     aligned) or, cwk64_egress_at with elem_bytes = 8, 8 bytes (8-byte aligned).  A position whose index is
+//                     >= batch gets zeros and atomicMin(d_bad, position); d_bad may be nullptr, the caller fills it first.
+//                     cwk_gather_at with `remap` (n_remap entries) reads instance remap[d_idx[j]] of its table and leaves the
+//                     rows alone whose entry is negative: the rows of a side batch written over those of the bit table.
+hipError_t cwk_select(hipStream_t s, const uint32_t *status, uint32_t batch, uint32_t mask, uint32_t want, const int32_t *fbidx,
+                      const uint32_t *fbstatus, uint32_t n_fb, uint32_t *counts, uint32_t *d_idx, uint32_t *d_n);
+hipError_t cwk_gather_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
+                         uint32_t n_idx, const uint32_t *d_n_idx, const int32_t *remap, uint32_t n_remap, void *d_out, uint32_t *d_bad,
+                         bool mont, const FpParams &P);
+hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t batch,
+                              const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t *d_bad);
+hipError_t cwk64_egress_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
+                           uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t elem_bytes, uint32_t *d_bad);
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,
                          uint32_t n_ichunks, const uint32_t *iterms, const uint32_t *itab, const uint32_t *irow_orig, const void *T,

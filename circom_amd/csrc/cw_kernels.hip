@@ -11,6 +11,7 @@
 #include "fp256.hip.h"
 #include "cw_rowops.hip.h"
 #include "cw_r1cs_products.h"
+#include "cw_select.h"
 
 #define CW_BLOCK 256
 
@@ -1036,6 +1037,85 @@ cw_gather_many_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ 
     }
 }
 
+// ---- egress by index (cw_get_witnesses_at*): out[j][k] = entry k of the range in instance idx[j] ---------------
+// cw_gather_many_kernel's tile (GM_TILE entries x 64 list positions, the same stage and the same 512-byte stores, conversion out
+// of Montgomery form per value); lane l reads column idx[i0 + l] of the table instead of first + i0 + l.  The index is loaded once
+// per thread, before the loop over the entries.
+//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list; with d_n the list ends
+//           at min(count, *d_n - pos0), read here: a workgroup whose tile lies behind it leaves at once (before its barrier),
+//           rows behind it are not written.
+//   bad     a position whose index is >= batch loads nothing, stages zeros and gets a row of zeros; after a ballot one lane of
+//           the tile's first workgroup reports the lowest such position, pos0 + i0 + l, with atomicMin (`bad` may be nullptr; the
+//           caller fills it first).
+//   remap   with a table `remap` of n_remap entries the lane reads column remap[idx] of THIS table, and a position whose entry
+//           is negative (or whose index is >= n_remap) is LEFT ALONE: this is how the instances a bit-plane batch re-ran are
+//           written over from the side batch's table in one launch, behind cw_bits_gather_at_kernel (which reports the bad ones).
+//   LDS     keep[64], one dword per list position, written by wave 0 (64 consecutive dwords: every bank at most once per group
+//           of 32 lanes) and read in the store loop, where the lanes of a store instruction cover 64 / (2 GM_TILE) positions:
+//           that many distinct addresses, the lanes that share one are served by a broadcast.  The tile itself is accessed as
+//           cw_gather_many_kernel accesses it (rows of 65 uint4).
+template <bool MONT>
+__global__ void __launch_bounds__(256)
+cw_gather_at_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch,
+                    const uint32_t *__restrict__ idx, uint32_t count, uint32_t pos0, const uint32_t *__restrict__ d_n,
+                    const int32_t *__restrict__ remap, uint32_t n_remap, uint4 *__restrict__ out, uint32_t *bad, FpParams P) {
+    __shared__ uint4 tile[GM_TILE][2][65];                          // [element][half][position] (+1: bank spread)
+    __shared__ uint32_t keep[64];
+    const uint32_t k0 = blockIdx.x * GM_TILE, i0 = blockIdx.y * 64;
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;  // 4 waves
+    uint32_t lim = count;
+    if (d_n) {
+        const uint32_t dn = *d_n, left = dn > pos0 ? dn - pos0 : 0u;
+        lim = left < lim ? left : lim;
+    }
+    if (i0 >= lim) return;                                          // the whole workgroup
+    const bool live = i0 + lane < lim;
+    uint32_t inst = live ? idx[i0 + lane] : 0u;
+    bool ok;
+    if (remap) {
+        const int32_t r = live && inst < n_remap ? remap[inst] : -1;
+        ok = r >= 0 && (uint32_t)r < batch;
+        inst = (uint32_t)r;
+    } else {
+        ok = live && inst < batch;
+        const uint64_t off = __ballot(live && !ok);
+        if (bad && off && blockIdx.x == 0 && threadIdx.x == 0) atomicMin(bad, pos0 + i0 + (uint32_t)__builtin_ctzll(off));
+    }
+    if (wv == 0) keep[lane] = remap ? ok : live;
+    for (uint32_t e = wv; e < GM_TILE; e += 4) {
+        const uint32_t k = k0 + e;
+        if (k < n_wit) {
+            uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+            if (ok) {
+                const size_t base = (size_t)w2s[k] * 2 * Bp + inst;
+                lo = V[base];
+                hi = V[base + Bp];
+                if (MONT) {
+                    fe x;
+                    x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
+                    x = fe_mmul(x, fe_small(1), P);
+                    lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+                    hi = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+                }
+            }
+            tile[e][0][lane] = lo;
+            tile[e][1][lane] = hi;
+        }
+    }
+    __syncthreads();
+    constexpr uint32_t PIECES = 2 * GM_TILE, PER = 64 / PIECES;
+    const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
+    for (uint32_t ii = wv * PER + sub; ii < 64; ii += 4 * PER) {
+        const uint32_t k = k0 + e;
+        if (k < n_wit && keep[ii]) {
+            const uint4 v = tile[e][h][ii];
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            u32x4 w = {v.x, v.y, v.z, v.w};
+            __builtin_nontemporal_store(w, (u32x4 *)&out[((size_t)(i0 + ii) * n_wit + k) * 2 + h]);
+        }
+    }
+}
+
 // ---- witness bits as packed rows (cw_get_witness_rows*) -----------------------------------------------------
 // Entry k of the list (w2s points at the range's first entry) of instance first + j becomes bit k & 63 of word k >> 6 of rows[j]
 // (MSB: the bits of each byte the other way round), 1 if and only if the value is 1.  The shape of the 64-bit runtime's kernel
@@ -1322,6 +1402,104 @@ hipError_t cwk_fill32(hipStream_t s, uint32_t *p, uint32_t v, size_t n) {
     hipLaunchKernelGGL(cw_fill32_kernel, dim3((unsigned)((n + CW_BLOCK - 1) / CW_BLOCK)), dim3(CW_BLOCK), 0, s, p, v, n);
     return hipGetLastError();
 }
+// ---- select by status (cw_select_instances*): idx[0 .. *total) = the instances i with (status[i] & mask) == want, ascending ----
+// An ordered stream compaction in three launches, so that no workgroup ever waits for another one (the stream orders them):
+//   count    cw_select_block_kernel<false>: a workgroup of four waves owns SEL_BLOCK = 2 048 consecutive instances, wave w the 512
+//            from 512 w, in 8 rounds of 64 (lane = instance: coalesced 256-byte loads of the words); a ballot and a popcount per
+//            round; counts[block] = the block's matches
+//   scan     cw_select_scan_kernel: ONE workgroup of 1 024 threads turns counts[] into exclusive prefix sums, 1 024 blocks per pass
+//            of its loop with the running sum carried along (2 097 152 instances are 1 024 blocks: one pass; there is no second
+//            level), and writes the total
+//   scatter  cw_select_block_kernel<true>: the same ballots again; a match's place is the block's prefix + the matches of the
+//            waves before its own + those of the rounds before + popcount(ballot below the lane): ascending order by construction
+// A status word is a status word: one kernel set for every engine.  For a bit-plane batch `fbidx` (instance -> position in the
+// side batch, or negative) and `fbstatus` (the side batch's words, n_fb of them) are given: a re-run instance is judged by the
+// side batch's word, as cw_get_status reports it.
+// LDS: part[4] / wsum[16], one dword per wave, written by one lane of each wave and read by all after the barrier: one address
+// per read instruction, a broadcast.
+static_assert(cwsel::SEL_BLOCK == 4 * 8 * 64 && cwsel::SCAN_WIDTH == 1024, "the geometry of the select kernels");
+template <bool SCATTER>
+__global__ void __launch_bounds__(256)
+cw_select_block_kernel(const uint32_t *__restrict__ status, uint32_t batch, uint32_t mask, uint32_t want, const int32_t *__restrict__ fbidx,
+                       const uint32_t *__restrict__ fbstatus, uint32_t n_fb, uint32_t *__restrict__ counts, uint32_t *__restrict__ idx) {
+    __shared__ uint32_t part[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t i0 = (uint64_t)blockIdx.x * cwsel::SEL_BLOCK + wave * 512u + lane;      // (64 bits: the last block of a batch next to 2^32)
+    uint64_t m[8];
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++) {
+        const uint64_t i = i0 + r * 64u;
+        bool hit = false;
+        if (i < batch) {
+            uint32_t w = status[i];
+            if (fbidx) {
+                const int32_t k = fbidx[i];
+                if (k >= 0 && (uint32_t)k < n_fb) w = fbstatus[k];
+            }
+            hit = (w & mask) == want;
+        }
+        m[r] = __ballot(hit);
+        mine += (uint32_t)__popcll(m[r]);
+    }
+    if (lane == 0) part[wave] = mine;
+    __syncthreads();
+    if (!SCATTER) {
+        if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+        return;
+    }
+    uint32_t at = counts[blockIdx.x];
+    for (uint32_t w = 0; w < wave; w++) at += part[w];
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++) {
+        if ((m[r] >> lane) & 1) idx[at + (uint32_t)__popcll(m[r] & below)] = (uint32_t)(i0 + r * 64u);
+        at += (uint32_t)__popcll(m[r]);
+    }
+}
+__global__ void __launch_bounds__(1024) cw_select_scan_kernel(uint32_t *__restrict__ counts, uint32_t n, uint32_t *__restrict__ total) {
+    __shared__ uint32_t wsum[16];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += cwsel::SCAN_WIDTH) {       // (n <= 2^21 blocks: base cannot wrap)
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n ? counts[i] : 0u;
+        uint32_t x = v;                                                   // inclusive scan of the wave
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < 16; w++) {
+            const uint32_t t = wsum[w];
+            before += w < wave ? t : 0u;
+            all += t;
+        }
+        if (i < n) counts[i] = carry + before + x - v;
+        carry += all;
+        __syncthreads();                                                  // wsum is written again by the next pass
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+// counts: scratch of cwsel::n_blocks(batch) words; d_idx == nullptr: count only (no scatter).  Nothing behind a launch that failed.
+hipError_t cwk_select(hipStream_t s, const uint32_t *status, uint32_t batch, uint32_t mask, uint32_t want, const int32_t *fbidx,
+                      const uint32_t *fbstatus, uint32_t n_fb, uint32_t *counts, uint32_t *d_idx, uint32_t *d_n) {
+    if (!status || !counts || !d_n || (fbidx && !fbstatus) || (((uintptr_t)d_idx | (uintptr_t)d_n) & 3)) return hipErrorInvalidValue;
+    const uint32_t nb = cwsel::n_blocks(batch);
+    if (nb)
+        hipLaunchKernelGGL(cw_select_block_kernel<false>, dim3(nb), dim3(256), 0, s, status, batch, mask, want, fbidx, fbstatus, n_fb, counts,
+                           (uint32_t *)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cw_select_scan_kernel, dim3(1), dim3(1024), 0, s, counts, nb, d_n);
+    e = hipGetLastError();
+    if (e != hipSuccess || !d_idx || !nb) return e;
+    hipLaunchKernelGGL(cw_select_block_kernel<true>, dim3(nb), dim3(256), 0, s, status, batch, mask, want, fbidx, fbstatus, n_fb, counts, d_idx);
+    return hipGetLastError();
+}
 // Boolean inputs as packed rows (cw_set_inputs_rows*, cw_rows.h) for the engines that ingest an image of values: input k of
 // instance j is one bit of rows[j * stride + (k >> 3)] and becomes the EB-byte value 0 / 1 at out[j][k] - the image cw_run's own
 // ingest kernels take (EB = 8: the 64-bit runtime, 32: the 256-bit schedule).  One thread per (instance, input), consecutive
@@ -1413,6 +1591,22 @@ hipError_t cwk_gather_many(hipStream_t s, const void *V, const uint32_t *w2s, ui
     else
         hipLaunchKernelGGL(cw_gather_many_kernel<false>, g, dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp, first, count, (uint4 *)out, P);
     return hipGetLastError();
+}
+// egress by index from the 8 x u32 table: entry tiles in gridDim.x, tiles of 64 list positions in gridDim.y - a launch holds at
+// most 65 535 of those, a longer list goes in several launches (cw_pieces.h), none behind one that failed.  `bad` (or nullptr)
+// takes an atomicMin of the lowest position whose index is >= batch; the caller fills it first.  With `remap` the positions whose
+// remap entry is negative are left alone and nothing is reported.
+hipError_t cwk_gather_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
+                         uint32_t n_idx, const uint32_t *d_n_idx, const int32_t *remap, uint32_t n_remap, void *d_out, uint32_t *d_bad,
+                         bool mont, const FpParams &P) {
+    if (!n_idx || !n_wit) return hipSuccess;
+    if (((uintptr_t)d_out & 15) || (((uintptr_t)d_idx | (uintptr_t)d_n_idx | (uintptr_t)d_bad) & 3)) return hipErrorInvalidValue;
+    const auto kernel = mont ? cw_gather_at_kernel<true> : cw_gather_at_kernel<false>;
+    return cw_pieces(n_idx, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + GM_TILE - 1) / GM_TILE, (m + 63) / 64), dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp, batch,
+                           d_idx + done, m, done, d_n_idx, remap, n_remap, (uint4 *)d_out + (size_t)done * n_wit * 2, remap ? nullptr : d_bad, P);
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_mulbench(hipStream_t s, const void *a, const void *b, void *out, uint32_t n, uint32_t iters,
                         const FpParams &P) {

@@ -33,7 +33,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -116,6 +116,12 @@ _SIGS = {
     "cw_get_r1cs_first_bad": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_r1cs_products": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_get_r1cs_products_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_select_instances": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "cw_select_instances_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cw_get_witnesses_at": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cw_get_witnesses_at_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cw_get_witnesses_at_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_get_witnesses_at_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_write_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtnsb": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cw_set_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -463,6 +469,44 @@ class Batch:
         """the same into device memory: [count][P][n_rows][element_bytes] at d_ptr, aligned to 8 bytes (64-bit runtime) or 16;
         asynchronous on the batch's stream (cw_get_r1cs_products_device)"""
         _chk(lib().cw_get_r1cs_products_device(self.h, parts, row0, n_rows, first, count, C.c_void_p(d_ptr)))
+
+    # -- instance lists: select by status on the device, egress by index ------------------------------------
+    def select(self, mask: int = 0xFFFFFFFF, want: int = 0) -> np.ndarray:
+        """the instances whose status word satisfies (status & mask) == want, ascending, uint32 (cw_select_instances); the
+        defaults select the clean instances, mask = want = ST_R1CS_FAILED those that failed the check"""
+        idx = np.zeros(self.n, dtype=np.uint32)
+        n = C.c_uint32(0)
+        _chk(lib().cw_select_instances(self.h, mask & 0xFFFFFFFF, want & 0xFFFFFFFF, idx.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return idx[:n.value].copy()
+
+    def select_device(self, mask: int, want: int, d_idx: int, d_n: int) -> None:
+        """the same into device memory: d_idx has room for `batch` uint32, d_n is one uint32, both 4-byte aligned; asynchronous on
+        the batch's stream (cw_select_instances_device)"""
+        _chk(lib().cw_select_instances_device(self.h, mask & 0xFFFFFFFF, want & 0xFFFFFFFF, C.c_void_p(d_idx), C.c_void_p(d_n)))
+
+    def witnesses_at(self, idx, entry0: int = 0, n: int | None = None) -> np.ndarray:
+        """uint8 [len(idx)][n][32]: entries [entry0, entry0 + n) of the witness list of the instances idx[j], in the list's order
+        (any order, repeats allowed), canonical little-endian (cw_get_witnesses_at); n=None: up to the end of the witness"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        n = self.circuit.n_witness - entry0 if n is None else n
+        out = np.zeros((len(idx), max(n, 0), 32), dtype=np.uint8)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the ranges)
+        spare = C.create_string_buffer(8)
+        ptr = out.ctypes.data_as(C.c_void_p) if out.size else C.cast(spare, C.c_void_p)
+        iptr = idx.ctypes.data_as(C.c_void_p) if idx.size else C.cast(spare, C.c_void_p)
+        _chk(lib().cw_get_witnesses_at(self.h, entry0, n, iptr, len(idx), ptr))
+        return out
+
+    def witnesses_at_device(self, d_idx: int, n_idx: int, d_out: int, entry0: int = 0, n: int | None = None, d_n_idx: int | None = None,
+                            d_bad: int | None = None, n8: bool = False) -> None:
+        """the same from a device list into device memory: [n_idx][n][32] at d_out (16-byte aligned), or, n8=True,
+        [n_idx][n][circuit.element_bytes].  d_n_idx: device address of a uint32, the list ends at min(n_idx, that) - the d_n of
+        select_device; d_bad: device address of a uint32 that takes the lowest position whose index is out of the batch (its row
+        is zeros) or 0xFFFFFFFF.  Launched inside the call, in stream order (cw_get_witnesses_at_device(_n8))"""
+        n = self.circuit.n_witness - entry0 if n is None else n
+        fn = lib().cw_get_witnesses_at_device_n8 if n8 else lib().cw_get_witnesses_at_device
+        _chk(fn(self.h, entry0, n, C.c_void_p(d_idx), n_idx, C.c_void_p(d_n_idx) if d_n_idx else None, C.c_void_p(d_out),
+                C.c_void_p(d_bad) if d_bad else None))
 
     def witness_bytes(self, instance: int) -> bytes:
         out = np.zeros(self.circuit.n_witness * 32, dtype=np.uint8)

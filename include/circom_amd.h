@@ -389,6 +389,60 @@ int cw_get_r1cs_first_bad(cw_batch *b, uint32_t *row);
 #define CW_R1CS_C 4u
 int cw_get_r1cs_products(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, uint8_t *out);
 int cw_get_r1cs_products_device(cw_batch *b, uint32_t parts, uint32_t row0, uint32_t n_rows, uint32_t first, uint32_t count, void *d_out);
+/* ---- instance lists: select by status on the device, egress by index, every engine --------------------------------------------
+ * Every egress above takes a contiguous range of instances.  A real batch is not uniformly good: a prover wants the witnesses of
+ * the clean instances as ONE dense image, an operator those of the failed ones.  cw_select_instances* makes the list on the
+ * device, cw_get_witnesses_at* hands out the witnesses of a list; chained through device memory the host reads neither the 4
+ * bytes per instance of cw_get_status nor the count.
+ *   select       the instances i with (status[i] & mask) == want, ascending, as uint32_t; status[i] is exactly the word
+ *                cw_get_status returns for i (bit-plane batches: the side batch's word for an instance it re-ran).  mask = ~0u,
+ *                want = 0: the clean instances; mask = want = CW_ST_R1CS_FAILED: those that failed the check; mask = want = 0:
+ *                all.  idx / d_idx have room for cw_batch_size entries; only the first *n are written, the rest keep their
+ *                bytes.  idx may be NULL (the host form then only counts); the device form needs both pointers, 4-byte aligned.
+ *                Before cw_check_r1cs the R1CS bit is simply not set.
+ *   image        out[j][k]: entry entry0 + k of the witness list (cw_set_witness_list order, as every other egress) of instance
+ *                idx[j], j < n_idx, k < n.  Dense: n_idx x n elements, offsets in 64-bit arithmetic.  The list may be in any
+ *                order and may name an instance twice.  The public signals of the listed instances: entry0 = 1, n = cw_n_public.
+ *   element      32 bytes, or cw_element_bytes in the _n8 forms (8 for the 64-bit runtime; for every other circuit they ARE the
+ *                32-byte calls): the canonical little-endian residue < q.  A table of Montgomery forms is converted on the way
+ *                out, as every other egress does.
+ *   host form    every index is validated before anything is touched: an index >= cw_batch_size is CW_EINVAL and the message
+ *                names its position.  The image is copied in pieces through a staging buffer; synchronises before it returns.
+ *   device form  the kernels are launched INSIDE the call: d_idx is read in stream order and may be reused once the batch's
+ *                stream has passed the call (the rule of cw_set_witnesses_device).  The host cannot see the list, so nothing is
+ *                read out of bounds: a position whose index is >= cw_batch_size gets a row of zeros, and the lowest such position
+ *                goes to *d_bad (optional, 4-byte aligned; 0xFFFFFFFF for a clean list; the call writes the word itself, in
+ *                stream order: a fill kernel, then atomicMin).  d_n_idx (optional, 4-byte aligned): the list ends at
+ *                min(n_idx, *d_n_idx), read on the device; rows behind it are not written.  So d_idx and d_n of
+ *                cw_select_instances_device feed the egress, n_idx = cw_batch_size, without the host reading the count: the grid
+ *                is sized by n_idx, workgroups behind the device count leave at once.  d_out: 16-byte aligned (8 bytes for the
+ *                8-byte element).
+ *   errors       in the order of the other getters: a null batch or pointer, entry0 + n > cw_n_witness (no 32-bit wrap), an index
+ *                of a host list out of the batch, an alignment as above (the pointer is not touched): CW_EINVAL.  Then the device
+ *                (a host-only batch: CW_EDEVICE), then the state: CW_ESTATE "... before cw_run" for a batch that has neither run
+ *                nor been supplied, "witnesses missing for N instances" for a supplied table with gaps, as cw_check_r1cs answers.
+ *   empty        n == 0 or n_idx == 0: CW_OK, no row is written; *d_bad (if given) becomes 0xFFFFFFFF.
+ *   lifetime     the host forms synchronise before they return.  The device forms are asynchronous on the batch's stream - with
+ *                the one exception of every device egress: the first call after a cw_run of a bit-plane batch waits for the
+ *                evaluation.  The calls only read: status words, first-bad rows, a captured cw_run_check graph and the supplied
+ *                state stay as they were.
+ *   memory       the select kernels keep 4 bytes per 2 048 instances (and the host form its list) with the batch; a bit-plane
+ *                batch uploads its instance -> side-batch map (4 bytes per instance) with the first call after a resolve.  All of
+ *                it is made on first use and freed with the batch; a batch that never asks pays nothing.
+ *   engines      select: csrc/cw_kernels.hip cw_select_block_kernel / cw_select_scan_kernel - count, scan, scatter as three
+ *                launches, no workgroup waits for another - for every engine.  Egress: 64-bit runtime (csrc/cw64.hip
+ *                cw64_egress_at_kernel, also in the supplied-witness state), 256-bit schedule (csrc/cw_kernels.hip
+ *                cw_gather_at_kernel, canonical and Montgomery-form tables), bit-plane batches (csrc/cw_bits.hip
+ *                cw_bits_gather_at_kernel, both table layouts; the rows of the instances the 256-bit side batch re-ran are written
+ *                over from there in one launch).  The tiles and stores of the range kernels, the column taken from the list. */
+int cw_select_instances(cw_batch *b, uint32_t mask, uint32_t want, uint32_t *idx, uint32_t *n);
+int cw_select_instances_device(cw_batch *b, uint32_t mask, uint32_t want, void *d_idx, void *d_n);
+int cw_get_witnesses_at(cw_batch *b, uint32_t entry0, uint32_t n, const uint32_t *idx, uint32_t n_idx, uint8_t *out);
+int cw_get_witnesses_at_n8(cw_batch *b, uint32_t entry0, uint32_t n, const uint32_t *idx, uint32_t n_idx, uint8_t *out);
+int cw_get_witnesses_at_device(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx,
+                               void *d_out, void *d_bad);
+int cw_get_witnesses_at_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx,
+                                  void *d_out, void *d_bad);
 /* host-only: build and hazard-check the LDS staging plan of the R1CS check kernel for `chunks` row chunks
    and `entries` 2-KiB LDS entries per wave (0 = the defaults cw_batch_create would pick for `batch`).
    out[8] = {chunks, loads, terms, filler loads, distinct wires, entries, prefetch depth, 0}. */
