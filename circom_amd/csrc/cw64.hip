@@ -15,6 +15,7 @@
 #include "cw_kernels.h"
 #include "cw_pieces.h"
 #include "cw_r1cs_products.h"
+#include "cw_columns.hip.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
 #define GL_HALF (GL_P >> 1)
@@ -64,6 +65,20 @@ __device__ __forceinline__ uint64_t gl_shr(uint64_t x, uint64_t y) {
     return k >= 64 ? 0 : gl_wrap(x << k);
 }
 
+// a 32-byte little-endian value w0 + w1 2^64 + w2 2^128 + w3 2^192 mod p, whatever its words hold: what cw64_ingest_kernel<32>
+// stores and what the input columns of 32-byte elements store (cw_columns.hip.h)
+__device__ __forceinline__ uint64_t gl_reduce256(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3) {
+    uint64_t r = gl_wrap(w0);
+    if (w1 | w2 | w3) {
+        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2, 2^192 = (2^32 - 1)^3 (mod p)
+        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e), e3 = gl_mul(e2, e);
+        r = gl_add(r, gl_mul(gl_wrap(w1), e));
+        r = gl_add(r, gl_mul(gl_wrap(w2), e2));
+        r = gl_add(r, gl_mul(gl_wrap(w3), e3));
+    }
+    return r;
+}
+
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) cw64_init_kernel(uint64_t *V, uint32_t Bp, uint32_t *status, uint32_t *first_bad) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -83,17 +98,7 @@ __global__ void __launch_bounds__(256) cw64_ingest_kernel(const uint64_t *__rest
     const uint32_t i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
     if (i >= batch) return;
     const uint64_t *p = in + ((size_t)i * n_in + k) * (EB / 8);
-    uint64_t r = p[0] >= GL_P ? p[0] - GL_P : p[0];
-    if (EB == 32) {
-        // 2^64 = 2^32 - 1, 2^128 = (2^32 - 1)^2, 2^192 = (2^32 - 1)^3 (mod p)
-        const uint64_t e = 0xFFFFFFFFull, e2 = gl_mul(e, e), e3 = gl_mul(e2, e);
-        if (p[1] | p[2] | p[3]) {
-            r = gl_add(r, gl_mul(p[1] >= GL_P ? p[1] - GL_P : p[1], e));
-            r = gl_add(r, gl_mul(p[2] >= GL_P ? p[2] - GL_P : p[2], e2));
-            r = gl_add(r, gl_mul(p[3] >= GL_P ? p[3] - GL_P : p[3], e3));
-        }
-    }
-    V[(size_t)(input_start + k) * Bp + i] = r;
+    V[(size_t)(input_start + k) * Bp + i] = EB == 32 ? gl_reduce256(p[0], p[1], p[2], p[3]) : gl_wrap(p[0]);
 }
 
 // row = 8 x u32: w0 = op | dk << 8 | ak << 10 | bk << 12 | ck << 14 (kind 0 = table slot, 2 = constant, 3 = none); dst; a; b; c;
@@ -715,6 +720,16 @@ hipError_t cwk64_ingest(hipStream_t s, const void *in, void *V, uint32_t input_s
     else
         hipLaunchKernelGGL(cw64_ingest_kernel<32>, grid, dim3(256), 0, s, (const uint64_t *)in, (uint64_t *)V, input_start, n_in, batch, Bp);
     return hipGetLastError();
+}
+// Input columns (cw_set_inputs_range*, cw_set_input_column*) into this runtime's image of 8-byte values (cw_columns.hip.h): an
+// 8-byte value >= p takes the one subtraction of cw64_ingest_kernel<8>, a 32-byte value the reduction of cw64_ingest_kernel<32>
+struct Cw64ColumnsReduce {
+    static __device__ __forceinline__ uint64_t wrap(uint64_t v) { return gl_wrap(v); }
+    static __device__ __forceinline__ uint64_t reduce4(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3) { return gl_reduce256(w0, w1, w2, w3); }
+};
+hipError_t cwk64_columns(hipStream_t s, const void *d_values, size_t stride, uint32_t n, uint32_t count, uint32_t width, void *out,
+                         size_t out_stride) {
+    return cw_columns_launch<8, Cw64ColumnsReduce>(s, d_values, stride, n, count, width, out, out_stride);
 }
 // The launches of cw64_transpose_in_kernel: elem_bytes = 8 (`in` 8-byte aligned) or 32 (16-byte aligned); a launch holds at most
 // 65 535 tiles of 64 instances (gridDim.y), larger counts are split as cwk64_egress splits them, and nothing more is launched

@@ -23,6 +23,7 @@
 #include "cw_rerun.h"
 #include "cw_pieces.h"
 #include "cw_rows.h"
+#include "cw_columns.h"
 #include "cw_r1cs_products.h"
 #include "cw_select.h"
 #include "cw_fn64.h"
@@ -1774,6 +1775,10 @@ struct cw_batch {
     std::vector<uint8_t> assigned; // [batch][n_in] flags (inputSignalAssigned, calcwit.cpp:28-32)
     std::vector<uint32_t> remaining;
     bool all_set = false, host_dirty = false, ran = false;
+    // input columns (cw_set_inputs_range*, cw_set_input_column*; cw_columns.h): the source is d_in and `col` records which inputs
+    // a column has covered since the state was opened; all_set follows col.missing == 0.  Ended by set_input_source alone.
+    bool col_state = false;
+    CwColumnCover col;
     // supplied witnesses (cw_set_witnesses*, cw_read_wtns*; 64-bit runtime): the table was filled by the caller, not by the witness
     // program.  wit_cover: one bit per instance that has been supplied since the first supply; wit_missing: the zero bits among
     // the batch's instances - what `remaining` is to the inputs
@@ -2313,6 +2318,10 @@ static void set_input_source(cw_batch *b, const void *ext, const void *packed, u
     b->packed_in = packed;
     b->in_eb = eb;
     b->host_dirty = dirty;
+    if (b->col_state) {                                   // any other setter ends the column state: a column call after it starts from
+        b->col_state = false;                             // empty coverage, and per-signal assignment counts in `remaining` again
+        b->all_set = false;
+    }
     if (complete) {
         b->all_set = true;
         std::fill(b->remaining.begin(), b->remaining.end(), 0);
@@ -2370,6 +2379,7 @@ extern "C" int cw_get_staged_input(cw_batch *b, uint32_t instance, uint32_t k, u
 extern "C" int64_t cw_remaining_inputs(const cw_batch *b, uint32_t instance) {
     if (!b || instance >= b->batch) return -1;
     if (b->all_set) return 0;
+    if (b->col_state) return b->col.missing;              // a column covers every instance: the same count for each
     return b->remaining[instance];
 }
 
@@ -2429,6 +2439,7 @@ static int ensure_d_pmask(cw_batch *b, size_t *n_bytes) {
     return CW_OK;
 }
 static uint32_t piece_rows(size_t row, uint32_t count);
+static int bits_resolve(cw_batch *b);
 extern "C" int cw_set_inputs_bits(cw_batch *b, const uint64_t *masks) {
     if (!b || !masks) return fail(CW_EINVAL, "null argument");
     NOT_FOR_64(b, "packed boolean inputs");
@@ -2518,6 +2529,142 @@ extern "C" int cw_set_inputs_rows(cw_batch *b, const uint8_t *rows, size_t strid
     rows_done(b);
     return CW_OK;
 }
+
+// ---- input columns (cw_columns.h, cw_columns.hip.h) ----
+// One named signal (or a range of main inputs) for the WHOLE batch from the array the caller holds: instance j's n values of
+// elem_bytes at values + j * stride go to [j][k0 + k] of the batch's own bulk image d_in, whose element is 8 bytes on the 64-bit
+// runtime and 32 bytes otherwise; cw_run ingests that image with the kernels it has, whatever the engine (a bit-plane batch
+// re-runs the instances whose values are not 0 / 1 from those bytes, as after cw_set_inputs).  The work happens INSIDE the call,
+// in stream order, by the rule of cw_set_inputs_rows*.
+//   state   the first call opens the column state (col_state; set_input_source, the funnel of every setter, ends it): the source
+//           is d_in, coverage is empty, all_set is false.  Each call covers [k0, k0 + n); all_set follows col.missing == 0.  The
+//           state survives cw_run / cw_run_check, so a later step updates any subset of columns and the rest of d_in stands; the
+//           graph key (image pointer, packed pointer, element size) does not change, and a replay ingests d_in as it then is.
+//   checks  null / elem_bytes / stride / alignment (CW_EINVAL), the name and the range (CW_EINPUT; the range forms: CW_EINVAL),
+//           the device.
+static uint32_t columns_eb(const cw_batch *b) { return b->c->is64 ? 8 : 32; }
+static int columns_args(cw_batch *b, const void *values, size_t stride, uint32_t n, uint32_t eb, bool device, const char *who) {
+    if (!b || !values) return fail(CW_EINVAL, std::string(who) + ": null argument");
+    if (const char *why = cw_columns_check(values, stride, n, eb, device)) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    return CW_OK;
+}
+// name, idx0, n -> k0, with the texts of cw_set_input_signal
+static int columns_resolve(const cw_batch *b, const char *name, uint32_t idx0, uint32_t n, uint32_t *k0) {
+    const cw_circuit *c = b->c;
+    const int64_t pos = hash_pos(c, fnv1a(name, strlen(name)));
+    if (pos < 0 || c->hashmap[pos].signalid == 0) return fail(CW_EINPUT, std::string("Signal not found: ") + name);
+    if ((uint64_t)idx0 + n > c->hashmap[pos].signalsize) return fail(CW_EINPUT, "Input signal array access exceeds the size");
+    *k0 = (uint32_t)c->hashmap[pos].signalid + idx0 - c->input_start;
+    return CW_OK;
+}
+// one launch: `count` instances from `first` on, from DEVICE rows
+static int columns_convert(cw_batch *b, const void *d_values, size_t stride, uint32_t k0, uint32_t n, uint32_t eb, uint32_t first, uint32_t count) {
+    const uint32_t ieb = columns_eb(b);
+    const size_t row = (size_t)b->c->n_inputs * ieb;
+    uint8_t *dst = (uint8_t *)b->d_in.get() + (size_t)first * row + (size_t)k0 * ieb;
+    if (b->c->is64) HIPCHK(cwk64_columns(b->stream, d_values, stride, n, count, eb, dst, row));
+    else HIPCHK(cwk_columns(b->stream, d_values, stride, n, count, eb, dst, row));
+    return CW_OK;
+}
+// The target of a column and the state it is written in.  A bit-plane batch that has run reads its inputs once more when the
+// instances to re-run are collected (bits_resolve): that happens before d_in is written again.
+static int columns_open(cw_batch *b) {
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = bits_resolve(b)) return rc;
+    if (int rc = ensure_d_in(b)) return rc;
+    if (!b->col_state) {
+        set_input_source(b, nullptr, nullptr, columns_eb(b), false, false);
+        b->col.open(b->c->n_inputs);
+        b->col_state = true;
+        b->all_set = false;
+    }
+    return CW_OK;
+}
+static void columns_cover(cw_batch *b, uint32_t k0, uint32_t n) {
+    b->col.cover(k0, n);
+    b->all_set = b->col.missing == 0;
+}
+static int columns_device(cw_batch *b, uint32_t k0, uint32_t n, const void *d_values, size_t stride, uint32_t eb) {
+    NEED_DEVICE(b);
+    if (!n) return CW_OK;
+    if (int rc = columns_open(b)) return rc;
+    if (int rc = columns_convert(b, d_values, stride, k0, n, eb, 0, b->batch)) return rc;
+    columns_cover(b, k0, n);
+    return CW_OK;
+}
+// Host values of any stride and alignment: dense rows are staged through d_bulk in pieces (cw_pieces / piece_rows), synchronised
+// before the staging buffer is written again and before returning; the broadcast form stages its one row once.  A host-only
+// batch stages each value zero-extended into h_in, unreduced, as set_inputs_host does, and counts the cells that were not assigned.
+static int columns_host(cw_batch *b, uint32_t k0, uint32_t n, const uint8_t *values, size_t stride, uint32_t eb) {
+    if (!n) return CW_OK;
+    const size_t row = cw_columns_row_bytes(n, eb);
+    if (b->device < 0) {
+        ensure_host_staging(b);
+        const uint32_t n_in = b->c->n_inputs;
+        for (size_t j = 0; j < b->batch; j++)
+            for (uint32_t k = 0; k < n; k++) {
+                const size_t cell = j * n_in + k0 + k;
+                cw_columns_widen(values + j * stride + (size_t)k * eb, eb, &b->h_in[cell * 32]);
+                if (!b->assigned[cell]) {
+                    b->assigned[cell] = 1;
+                    if (b->remaining[j]) b->remaining[j]--;
+                }
+            }
+        set_input_source(b, nullptr, nullptr, 32, true, false);
+        return CW_OK;
+    }
+    if (int rc = columns_open(b)) return rc;
+    if (!stride) {
+        HIPCHK(b->d_bulk.grow(row));
+        HIPCHK(hipMemcpyAsync(b->d_bulk, values, row, hipMemcpyHostToDevice, b->stream));
+        if (int rc = columns_convert(b, b->d_bulk, 0, k0, n, eb, 0, b->batch)) return rc;
+        HIPCHK(hipStreamSynchronize(b->stream));
+    } else {
+        const uint32_t per = piece_rows(row, b->batch);
+        std::vector<uint8_t> img(stride == row ? 0 : (size_t)per * row);     // dense rows are copied from where they are
+        HIPCHK(b->d_bulk.grow((size_t)per * row));
+        const int rc = cw_pieces(b->batch, per, [&](uint32_t done, uint32_t m) {
+            const uint8_t *from = values + (size_t)done * stride;
+            if (stride != row) {
+                cw_columns_repack(from, stride, n, eb, m, img.data());
+                from = img.data();
+            }
+            HIPCHK(hipMemcpyAsync(b->d_bulk, from, (size_t)m * row, hipMemcpyHostToDevice, b->stream));
+            if (int rc2 = columns_convert(b, b->d_bulk, row, k0, n, eb, done, m)) return rc2;
+            HIPCHK(hipStreamSynchronize(b->stream));
+            return CW_OK;
+        });
+        if (rc) return rc;
+    }
+    columns_cover(b, k0, n);
+    return CW_OK;
+}
+extern "C" int cw_set_inputs_range(cw_batch *b, uint32_t k0, uint32_t n, const void *values, size_t stride, uint32_t elem_bytes) {
+    if (int rc = columns_args(b, values, stride, n, elem_bytes, false, "cw_set_inputs_range")) return rc;
+    if (const char *why = cw_columns_check_range(k0, n, b->c->n_inputs)) return fail(CW_EINVAL, std::string("cw_set_inputs_range: ") + why);
+    return columns_host(b, k0, n, (const uint8_t *)values, stride, elem_bytes);
+}
+extern "C" int cw_set_inputs_range_device(cw_batch *b, uint32_t k0, uint32_t n, const void *d_values, size_t stride, uint32_t elem_bytes) {
+    if (int rc = columns_args(b, d_values, stride, n, elem_bytes, true, "cw_set_inputs_range_device")) return rc;
+    if (const char *why = cw_columns_check_range(k0, n, b->c->n_inputs)) return fail(CW_EINVAL, std::string("cw_set_inputs_range_device: ") + why);
+    return columns_device(b, k0, n, d_values, stride, elem_bytes);
+}
+extern "C" int cw_set_input_column(cw_batch *b, const char *name, uint32_t idx0, uint32_t n, const void *values, size_t stride, uint32_t elem_bytes) {
+    if (!name) return fail(CW_EINVAL, "cw_set_input_column: null argument");
+    if (int rc = columns_args(b, values, stride, n, elem_bytes, false, "cw_set_input_column")) return rc;
+    uint32_t k0 = 0;
+    if (int rc = columns_resolve(b, name, idx0, n, &k0)) return rc;
+    return columns_host(b, k0, n, (const uint8_t *)values, stride, elem_bytes);
+}
+extern "C" int cw_set_input_column_device(cw_batch *b, const char *name, uint32_t idx0, uint32_t n, const void *d_values, size_t stride,
+                                          uint32_t elem_bytes) {
+    if (!name) return fail(CW_EINVAL, "cw_set_input_column_device: null argument");
+    if (int rc = columns_args(b, d_values, stride, n, elem_bytes, true, "cw_set_input_column_device")) return rc;
+    uint32_t k0 = 0;
+    if (int rc = columns_resolve(b, name, idx0, n, &k0)) return rc;
+    return columns_device(b, k0, n, d_values, stride, elem_bytes);
+}
+extern "C" int64_t cw_inputs_missing(const cw_batch *b) { return b && b->col_state ? (int64_t)b->col.missing : -1; }
 
 // ---------------------------------------------------------------------------------------------------------
 // JSON ingest — loadJson / qualify_input / json2FrElements (main.cpp:144-286)
@@ -2943,7 +3090,9 @@ extern "C" int cw_run(cw_batch *b) {
     cw_circuit *c = b->c;
     if (!b->all_set) {
         uint64_t missing = 0;
-        for (uint32_t r : b->remaining) missing += r;
+        if (b->col_state) missing = (uint64_t)b->col.missing * b->batch;
+        else
+            for (uint32_t r : b->remaining) missing += r;
         if (missing) {
             // main.cpp:352-355
             return fail(CW_ESTATE, "Not all inputs have been set. " + std::to_string(missing) + " values missing over the batch");

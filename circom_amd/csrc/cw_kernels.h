@@ -59,6 +59,14 @@ hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void 
 hipError_t cwk_bits_rows_to_masks(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *d_masks);
 hipError_t cwk_rows_expand(hipStream_t s, const void *d_rows, size_t stride, uint32_t n_in, uint32_t batch, bool msb, void *out,
                            uint32_t elem_bytes);
+// input columns (cw_set_inputs_range*, cw_set_input_column*; cw_columns.h, cw_columns.hip.h): instance j's n values of `width`
+// bytes (1, 2, 4, 8 or 32; little-endian) at d_values + j * stride (0: the same n values for every instance) become the run
+// out + j * out_stride of n elements of 32 bytes (cwk_columns: values as they stand) or 8 bytes (cwk64_columns: 8- and 32-byte
+// values reduced mod p).  d_values and stride aligned to `width` (16 for 32), out and out_stride to 16 / 8.  One launch.
+hipError_t cwk_columns(hipStream_t s, const void *d_values, size_t stride, uint32_t n, uint32_t count, uint32_t width, void *out,
+                       size_t out_stride);
+hipError_t cwk64_columns(hipStream_t s, const void *d_values, size_t stride, uint32_t n, uint32_t count, uint32_t width, void *out,
+                         size_t out_stride);
 // witness bits OUT as packed rows (cw_get_witness_rows*, cw_rows.h), one kernel per table layout: entry k of the range (wslot / w2s
 // point at its first entry) of instance first + j = bit k & 7 (msb: 7 - (k & 7)) of byte k >> 3 of d_rows + j * stride, 1 iff the
 // value is 1; rows of 8 * ceil(n / 64) bytes are written, pad bits 0.  d_rows 8-byte aligned, stride a multiple of 8 and at least

@@ -12,6 +12,7 @@
 #include "cw_rowops.hip.h"
 #include "cw_r1cs_products.h"
 #include "cw_select.h"
+#include "cw_columns.hip.h"
 
 #define CW_BLOCK 256
 
@@ -1537,6 +1538,12 @@ hipError_t cwk_rows_expand(hipStream_t s, const void *d_rows, size_t stride, uin
         hipLaunchKernelGGL(cw_rows_expand_kernel<32>, dim3(blocks), dim3(CW_BLOCK), 0, s, (const uint8_t *)d_rows, stride, n_in, batch, msb ? 1u : 0u,
                            (uint8_t *)out);
     return hipGetLastError();
+}
+// Input columns (cw_set_inputs_range*, cw_set_input_column*) into an image of 32-byte values: cw_columns.hip.h.  The 64-bit
+// runtime's instantiations are cwk64_columns (cw64.hip).
+hipError_t cwk_columns(hipStream_t s, const void *d_values, size_t stride, uint32_t n, uint32_t count, uint32_t width, void *out,
+                       size_t out_stride) {
+    return cw_columns_launch<32, CwColumnsAsIs>(s, d_values, stride, n, count, width, out, out_stride);
 }
 hipError_t cwk_fused_merge(hipStream_t s, const uint32_t *found, uint32_t batch, uint32_t *status, uint32_t *first_bad) {
     hipLaunchKernelGGL(cw_fused_merge_kernel, blocks_for(batch), dim3(CW_BLOCK), 0, s, found, batch, status, first_bad);

@@ -33,7 +33,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -85,6 +85,11 @@ _SIGS = {
     "cw_set_inputs_bits_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_set_inputs_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
     "cw_set_inputs_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_set_inputs_range": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_set_inputs_range_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_set_input_column": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_set_input_column_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "cw_inputs_missing": (C.c_int64, [C.c_void_p]),
     "cw_stream_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_signal_slots": (C.POINTER(C.c_uint32), [C.c_void_p]),
     "cw_batch_signal_slots": (C.POINTER(C.c_uint32), [C.c_void_p]),
@@ -347,6 +352,60 @@ class Batch:
         """the same from device memory: 8-byte aligned, stride a multiple of 8 and >= 8 * ceil(n_inputs / 64); converted inside the
         call in stream order (cw_set_inputs_rows_device)"""
         _chk(lib().cw_set_inputs_rows_device(self.h, C.c_void_p(dptr), stride, ROWS_MSB_FIRST if msb_first else 0))
+
+    def _column_rows(self, arr, elem_bytes):
+        """(array kept alive, n, stride, elem_bytes) of the values of a column: [batch][n] of uint8 / uint16 / uint32 / uint64, or
+        [batch][n][32] uint8 (32-byte little-endian values); one dimension less ([n], or [n][32] with elem_bytes=32) is the
+        broadcast form, stride 0.  The row stride is the array's first stride (a view of a wider array keeps its padding); the
+        values of a row are contiguous."""
+        arr = np.asarray(arr)
+        assert arr.dtype in (np.uint8, np.uint16, np.uint32, np.uint64), "uint8 / uint16 / uint32 / uint64 values"
+        arr = arr.astype(arr.dtype.newbyteorder("<"), copy=False)
+        wide = elem_bytes == 32 if elem_bytes is not None else (arr.dtype == np.uint8 and arr.ndim == 3)
+        if wide:
+            assert arr.dtype == np.uint8 and arr.ndim in (2, 3) and arr.shape[-1] == 32, "32-byte values: a trailing axis of 32 uint8"
+            eb, dims = 32, arr.ndim - 1
+        else:
+            eb, dims = arr.dtype.itemsize, arr.ndim
+            assert elem_bytes in (None, eb), "elem_bytes does not match the dtype"
+        assert dims in (1, 2), "[n] (broadcast) or [batch][n] values"
+        if dims == 1:
+            arr = np.ascontiguousarray(arr)
+            return arr, arr.shape[0], 0, eb
+        assert arr.shape[0] == self.n, arr.shape
+        n = arr.shape[1]
+        dense = np.empty(arr.shape, dtype=arr.dtype).strides
+        if arr.strides[1:] != dense[1:] or arr.strides[0] < n * eb:     # the values of a row are not contiguous, or rows overlap
+            arr = np.ascontiguousarray(arr)
+        return arr, n, arr.strides[0], eb
+
+    def set_input_column(self, name: str, arr, idx0: int = 0, elem_bytes: int | None = None):
+        """elements idx0 .. idx0 + n - 1 of input signal `name` for EVERY instance (cw_set_input_column).  arr: [batch][n] of
+        uint8 / uint16 / uint32 / uint64, or [batch][n][32] uint8 for 32-byte little-endian values - the width comes from the
+        dtype; a 1-D array of length n is the broadcast form (every instance takes the same n values; 32-byte values: [n][32]
+        with elem_bytes=32).  A scalar signal is a column of n = 1."""
+        arr, n, stride, eb = self._column_rows(arr, elem_bytes)
+        ptr = arr.ctypes.data_as(C.c_void_p) if arr.size else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _chk(lib().cw_set_input_column(self.h, name.encode(), idx0, n, ptr, stride, eb))
+
+    def set_input_column_device(self, name: str, dptr: int, n: int, stride: int, elem_bytes: int, idx0: int = 0):
+        """the same from device memory: instance j's n values of elem_bytes at dptr + j * stride (stride 0: broadcast); dptr and
+        stride multiples of elem_bytes (16 for 32-byte values).  Converted inside the call, in stream order: the buffer is free
+        once the batch's stream has passed the call (cw_set_input_column_device)"""
+        _chk(lib().cw_set_input_column_device(self.h, name.encode(), idx0, n, C.c_void_p(dptr), stride, elem_bytes))
+
+    def set_inputs_range(self, k0: int, arr, elem_bytes: int | None = None):
+        """inputs k0 .. k0 + n - 1 (main-input order) of every instance; arr as set_input_column takes it (cw_set_inputs_range)"""
+        arr, n, stride, eb = self._column_rows(arr, elem_bytes)
+        ptr = arr.ctypes.data_as(C.c_void_p) if arr.size else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _chk(lib().cw_set_inputs_range(self.h, k0, n, ptr, stride, eb))
+
+    def set_inputs_range_device(self, k0: int, dptr: int, n: int, stride: int, elem_bytes: int):
+        _chk(lib().cw_set_inputs_range_device(self.h, k0, n, C.c_void_p(dptr), stride, elem_bytes))
+
+    def inputs_missing(self) -> int:
+        """inputs no column has covered yet; -1 when the batch is not in the column state (cw_inputs_missing)"""
+        return lib().cw_inputs_missing(self.h)
 
     def stream_witnesses_device(self, first: int, count: int, chunk: int, d_buf0: int, d_buf1: int, consume):
         """consume(first, count, d_chunk, stream) -> int, called once per chunk (cw_stream_witnesses_device)"""

@@ -196,6 +196,54 @@ int cw_set_inputs_bits_device(cw_batch *b, const void *d_masks);
 #define CW_ROWS_MSB_FIRST 1u
 int cw_set_inputs_rows(cw_batch *b, const uint8_t *rows, size_t stride, uint32_t flags);
 int cw_set_inputs_rows_device(cw_batch *b, const void *d_rows, size_t stride, uint32_t flags);
+/* Input COLUMNS, every engine: one named signal (or a range of main inputs) for the WHOLE batch, from the array the caller
+ * already holds per signal - leaf[batch], pathElements[batch][20], sig[batch][3] - in host or device memory.  The caller needs
+ * neither the slot order nor an interleaved image, widens nothing itself, and updates one signal between two steps without
+ * rebuilding the rest.  cw_set_inputs_range* name the inputs k0 .. k0 + n - 1 in main-input order (as in the bulk forms);
+ * cw_set_input_column* name the elements idx0 .. idx0 + n - 1 of input signal `name`, the lookup of cw_set_input_signal and
+ * cw_input_size.
+ *   layout     instance j's values are the n little-endian unsigned integers of elem_bytes in {1, 2, 4, 8, 32} at
+ *              values + j * stride.  stride == 0 is the BROADCAST form: every instance takes the same n values (a Merkle root, a
+ *              public parameter).  Any other stride is at least n * elem_bytes; bytes of a row behind the n values are never read.
+ *   values     widths 1 to 8 are canonical for every 4-limb prime.  64-bit runtime (--prime goldilocks): an 8-byte value >= p
+ *              is reduced with one subtraction, as cw_set_inputs_n8 reduces it, and a 32-byte value over all four words.  Every
+ *              other engine takes a 32-byte value by the rule of cw_set_inputs: canonical, reduced by the caller.
+ *   target     the batch's own bulk image, [batch][n_inputs][element] with the element of 8 bytes on the 64-bit runtime and 32
+ *              bytes otherwise, at [j][k0 + k].  cw_run ingests that image with the kernels it has (Montgomery conversion, tiled
+ *              transpose, bit-plane ingest), so the calls are correct on every engine by construction; the instances of a
+ *              bit-plane batch whose values are not 0 / 1 are re-run by the 256-bit schedule from those bytes, as after
+ *              cw_set_inputs.  A bit-plane batch therefore pays 32 bytes per input BIT here and allocates batch * n_inputs * 32
+ *              bytes with its first column: large boolean batches belong to cw_set_inputs_rows* and cw_set_inputs_bits*.
+ *   state      the first range / column call on a batch whose inputs come from anything else opens the COLUMN STATE: nothing is
+ *              covered.  Each call covers [k0, k0 + n) for every instance; covering an input again overwrites it (a bulk form:
+ *              there is no "assigned twice").  cw_inputs_missing: the inputs no column has covered yet, -1 when the batch is not
+ *              in the column state; cw_remaining_inputs(b, i) returns the same count for every i.  cw_run with inputs missing
+ *              answers CW_ESTATE "Not all inputs have been set. N values missing over the batch", N = missing inputs x batch.
+ *              The state SURVIVES cw_run and cw_run_check: a later step updates any subset of columns and the rest of the image
+ *              stands.  The input key of cw_run_check's graph does not change, so a captured graph is replayed over the new
+ *              values.  Every other setter ends the column state (the latest setter wins); a column call after it starts from
+ *              empty coverage.
+ *   lifetime   the rule of cw_set_inputs_rows*.  The device forms launch the conversion (csrc/cw_columns.hip.h cw_columns_kernel)
+ *              INSIDE the call, in stream order: the buffer may be reused once the batch's stream has passed the call.  The host
+ *              forms take any alignment, stage dense rows through a device buffer in pieces and synchronise before they return.
+ *              A bit-plane batch that has run first waits for that run and collects the instances to re-run (what the first
+ *              cw_sync / getter after cw_run does), since that step reads the image a column is about to change.
+ *   checks     in this order: a null pointer, elem_bytes, a stride shorter than the row, and, device forms, d_values or a
+ *              non-zero stride that is no multiple of elem_bytes (of 16 for 32-byte elements): CW_EINVAL - the pointer is never
+ *              touched.  Then the name and the range: CW_EINPUT "Signal not found: <name>" / "Input signal array access exceeds
+ *              the size" (idx0 + n beyond the signal); the range forms: k0 + n > cw_n_inputs is CW_EINVAL.  Then the device: a
+ *              host-only batch answers CW_EDEVICE to the device forms.  n == 0 is CW_OK and covers nothing.
+ *   host-only  the host forms stage each value into the staging image of the per-signal setters, zero-extended to 32 bytes and
+ *              unreduced, for every instance: cw_get_staged_input returns it, cw_remaining_inputs falls by the cells that were
+ *              not assigned before.  There is no column state on such a batch.
+ *   not here   instance sub-ranges (a column always spans the batch); writing the value table or the packed masks directly;
+ *              supplied witnesses (cw_set_witnesses*). */
+int cw_set_inputs_range(cw_batch *b, uint32_t k0, uint32_t n, const void *values, size_t stride, uint32_t elem_bytes);
+int cw_set_inputs_range_device(cw_batch *b, uint32_t k0, uint32_t n, const void *d_values, size_t stride, uint32_t elem_bytes);
+int cw_set_input_column(cw_batch *b, const char *name, uint32_t idx0, uint32_t n, const void *values, size_t stride, uint32_t elem_bytes);
+int cw_set_input_column_device(cw_batch *b, const char *name, uint32_t idx0, uint32_t n, const void *d_values, size_t stride,
+                               uint32_t elem_bytes);
+int64_t cw_inputs_missing(const cw_batch *b);
 /* read back input k (slot cw_input_start()+k) of one instance as staged by the two per-signal setters */
 int cw_get_staged_input(cw_batch *b, uint32_t instance, uint32_t k, uint8_t out[32]);
 /* getRemaingInputsToBeSet() (calcwit.hpp:50-52) of one instance */
