@@ -1855,6 +1855,21 @@ static hipError_t upload(DevBuf<T> *dst, const std::vector<T> &src, hipStream_t 
     return e;
 }
 
+// Drops cw_run_check's captured step (new input pointers, timing marks, host inputs, cw_device_bits).  The batch's stream is
+// drained first: the caller need not have synchronised since the last cw_run_check, so a replay may still be in flight on
+// b->stream, and destroying a graph exec under its own replay is undefined.  Dropping is rare (never inside a steady loop), so
+// the wait costs nothing that is measured.
+static void drop_rc_graph(cw_batch *b) {
+    if (!b->rc_graph) return;
+    if (b->device >= 0) {
+        hipSetDevice(b->device);
+        hipStreamSynchronize(b->stream);
+    }
+    hipGraphExecDestroy(b->rc_graph);
+    b->rc_graph = nullptr;
+    b->rc_calls = 0;
+}
+
 // The stream is drained first: a replay of the captured graph may be in flight until then, and it uses the graph exec and
 // every table of the batch.  The d_* members free themselves when the batch is deleted.
 extern "C" void cw_batch_free(cw_batch *b) {
@@ -3321,11 +3336,7 @@ extern "C" int cw_run_check(cw_batch *b) {
     };
     const InputKey key = input_key(b);
     const bool same = key == b->rc_key;
-    if (b->rc_graph && (!same || b->timing || b->host_dirty)) {
-        hipGraphExecDestroy(b->rc_graph);
-        b->rc_graph = nullptr;
-        b->rc_calls = 0;
-    }
+    if (b->rc_graph && (!same || b->timing || b->host_dirty)) drop_rc_graph(b);
     if (b->timing || b->host_dirty || b->rc_failed || getenv("CW_NO_GRAPH")) return plain();
     if (!b->rc_graph) {
         if (!same) {
@@ -4326,11 +4337,7 @@ extern "C" void *cw_device_bits(cw_batch *b, uint64_t *n_bytes, uint64_t *slots_
     if (!b || !b->bitmode) return nullptr;
     if (n_bytes) *n_bytes = b->t_bytes;
     if (slots_per_group) *slots_per_group = b->bits_slots;
-    if (b->rc_graph) {                      // (cw_run_check's graph holds the check that trusts the table)
-        hipGraphExecDestroy(b->rc_graph);
-        b->rc_graph = nullptr;
-        b->rc_calls = 0;
-    }
+    drop_rc_graph(b);                       // (cw_run_check's graph holds the check that trusts the table)
     b->table_dirty = true;                  // the caller may write through the pointer: the next R1CS check audits the table itself
     return b->d_T;
 }
