@@ -18,6 +18,7 @@
 // result is the reference's for every input.
 #include <hip/hip_runtime.h>
 #include "cw_kernels.h"
+#include "cw_bits_layout.h"
 #include "cw_pieces.h"
 #include "cw_r1cs_products.h"
 #include "fp256.hip.h"
@@ -33,12 +34,13 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 //                                                instances, a slot of a chunk = one 256-byte row (lane l of the emitting wave
 //                                                holds dword l: instances 32 l .. 32 l + 31 of the chunk)
 // element (group g, slot s) = T[(((g >> sh) * slots + s) << sh) + (g & ((1 << sh) - 1))]: the slots of a group are
-// (1 << sh) uint64 apart, starting at bits_group(T, slots, sh, g).
+// (1 << sh) uint64 apart, starting at bits_group(T, slots, sh, g).  The formula itself is cw_bits_layout.h's (HIP-free: a host
+// test walks the same lines).
 __device__ __forceinline__ uint64_t *bits_group(uint64_t *T, uint64_t slots, uint32_t sh, uint32_t g) {
-    return T + (((size_t)(g >> sh) * slots) << sh) + (g & ((1u << sh) - 1u));
+    return T + cwlayout::group_base(slots, sh, g);
 }
 __device__ __forceinline__ const uint64_t *bits_group(const uint64_t *T, uint64_t slots, uint32_t sh, uint32_t g) {
-    return T + (((size_t)(g >> sh) * slots) << sh) + (g & ((1u << sh) - 1u));
+    return T + cwlayout::group_base(slots, sh, g);
 }
 
 // ---- init: constant slots, flags -------------------------------------------------------------------------------------
@@ -75,6 +77,13 @@ __global__ void __launch_bounds__(256) cw_bits_init_kernel(uint64_t *T, uint64_t
 //   chunks fastest + every group starts at its own instance (hash(g) & 63)      23.4 ms
 //   that, four waves per workgroup on consecutive chunks, unrolled x 4          22.2 ms   6.19 TB/s   <- this kernel
 //   (two waves 22.6, eight 23.2, sixteen 23.3; unrolled x 2 22.9, x 8 22.5; no rotation 24.0-24.4)
+// Where the final store lands is the caller's choice of (T, slots, sh, input_slot0).  Into the interpreter's table (sh = 0) a
+// wave's store is 512 contiguous bytes.  Into the emitted code's table (sh = 5) its 64 lanes would hit 64 different 256-byte rows,
+// 8 bytes each, and the 32 groups that complete a row belong to 32 workgroups that finish at different times: 67 M write requests
+// of one 64-byte piece per 8 bytes of payload at the benchmark shape.  An emitted-code batch therefore points this kernel at a
+// staging buffer of packed masks (cw_host.cpp bits_run: T = d_stage, slots = n_in, sh = 0, input_slot0 = 0, which IS
+// masks[group][k]) and cw_bits_masks_to_table_rows_kernel below writes the table from there in whole rows.  This kernel's source
+// and launch geometry are the same on both routes.
 #define BITS_INGEST_WAVES 4
 __global__ void __launch_bounds__(64 * BITS_INGEST_WAVES)
 cw_bits_ingest_kernel(const uint4 *__restrict__ in, uint64_t *__restrict__ T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
@@ -581,6 +590,56 @@ cw_bits_ingest_packed_kernel(const uint64_t *__restrict__ masks, uint64_t *__res
     if (live < 64) m &= (1ull << live) - 1;
     bits_group(T, slots, sh, g)[(size_t)(input_slot0 + k) << sh] = m;
 }
+// The same into the emitted code's table (sh = 5, T[chunk][slot][32 groups]) in WHOLE ROWS.  With the kernel above a wave's store
+// there is 64 pieces of 8 bytes in 64 different 256-byte rows; here a workgroup of four waves owns a tile of one chunk (32 groups)
+// x 64 inputs and transposes it through LDS (index arithmetic: cw_bits_layout.h, replayed on the CPU by
+// tests/host/bits_rows_layout_test.cpp).  Grid: chunks in x, tiles of 64 inputs in y.
+//   read    wave w takes the groups w, w + 4, .. w + 28 of the chunk, lane l the input k0 + l: a load is 512 contiguous bytes of
+//           masks[g][...]; the eight loads stand in one straight-line block ahead of the first LDS write.  Groups >= n_groups
+//           (the padding of the last chunk) and inputs >= n_in read as 0; the last real group is masked to its live instances
+//   stage   tile[group][input] with rows of 65 words of 8 bytes (16 640 bytes), the padding of cw_bits_rows_to_masks_kernel's tile.
+//           Row-wise write (ds_write_b64: four groups of 16 consecutive lanes, bank = (a/4) % 32): 16 consecutive words = 32
+//           consecutive dwords, every bank once.  Column-wise read (ds_read_b64: two groups of 32 lanes, bank = (a/4) % 64): the 32
+//           lanes of a half-wave have gl = 0 .. 31 at one kk, word 65 gl + kk, dwords 130 gl + 2 kk and the next one, bank pair
+//           (2 gl + 2 kk) % 64: 32 distinct pairs.  Zero conflicts in both directions by this arithmetic from the documented bank
+//           rules; no bank-conflict counter pass was taken on this kernel.
+//   write   store r of thread t is cell r * 256 + t of the tile counted inputs first (kk = idx >> 5, gl = idx & 31): consecutive
+//           input slots are consecutive rows of the chunk, so 32 threads write one 256-byte row, a store instruction of the
+//           workgroup 2 KiB contiguous, a full tile one contiguous 16 KiB.  Rows of inputs >= n_in are not written.
+// The padding groups' columns of the input rows get zeros (valid bits), where the kernel above leaves what the allocation held.
+__global__ void __launch_bounds__(cwlayout::ROWS_THREADS)
+cw_bits_masks_to_table_rows_kernel(const uint64_t *__restrict__ masks, uint64_t *__restrict__ T, uint64_t slots, uint32_t input_slot0,
+                                   uint32_t n_in, uint32_t batch, uint32_t n_groups) {
+    using namespace cwlayout;
+    __shared__ uint64_t tile[ROWS_GROUPS * ROWS_STRIDE];
+    const uint32_t chunk = blockIdx.x, k0 = blockIdx.y * ROWS_INPUTS, g0 = chunk * ROWS_GROUPS;
+    uint64_t v[ROWS_LOADS] = {};
+    {
+        const uint32_t k = k0 + rows_read_cell(threadIdx.x, 0).kk;
+        if (k < n_in) {
+            // a padding group loads the last real group's mask (valid memory) and drops it: the loads carry no condition of their
+            // own, so the compiler keeps all eight in flight in the last chunk too
+#pragma unroll
+            for (uint32_t j = 0; j < ROWS_LOADS; j++) {
+                const uint32_t g = g0 + rows_read_cell(threadIdx.x, j).gl;
+                v[j] = masks[(size_t)(g < n_groups ? g : n_groups - 1u) * n_in + k];
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < ROWS_LOADS; j++) {
+                const uint32_t g = g0 + rows_read_cell(threadIdx.x, j).gl;
+                v[j] = g < n_groups ? v[j] & rows_live_mask(batch, g) : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < ROWS_LOADS; j++) tile[rows_tile_word(rows_read_cell(threadIdx.x, j))] = v[j];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < ROWS_STORES; r++) {
+        const RowsCell c = rows_write_cell(threadIdx.x, r);
+        if (k0 + c.kk < n_in) T[element(slots, ROWS_SH, g0 + c.gl, (uint64_t)input_slot0 + k0 + c.kk)] = tile[rows_tile_word(c)];
+    }
+}
 // canonical inputs of the listed instances from packed masks / from the AoS input image (rows of the side batch that
 // re-runs them on the 256-bit schedule): out[j][k] = input k of instance inst[j]
 __global__ void __launch_bounds__(256)
@@ -1077,6 +1136,15 @@ hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint
 hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                                   uint32_t batch) {
     if (n_in == 0) return hipSuccess;
+    // the emitted code's table: whole rows (chunks in x, input tiles in y; beyond 65 535 tiles = 4 194 240 inputs the kernel below
+    // still serves the launch)
+    if (sh == cwlayout::ROWS_SH && batch && (n_in + cwlayout::ROWS_INPUTS - 1) / cwlayout::ROWS_INPUTS <= 65535u) {
+        const uint32_t n_groups = (batch >> 6) + ((batch & 63u) != 0);
+        const dim3 grid((n_groups + cwlayout::ROWS_GROUPS - 1) / cwlayout::ROWS_GROUPS, (n_in + cwlayout::ROWS_INPUTS - 1) / cwlayout::ROWS_INPUTS);
+        hipLaunchKernelGGL(cw_bits_masks_to_table_rows_kernel, grid, dim3(cwlayout::ROWS_THREADS), 0, s, (const uint64_t *)masks, (uint64_t *)T,
+                           slots, input_slot0, n_in, batch, n_groups);
+        return hipGetLastError();
+    }
     dim3 g((batch + 63) / 64, (n_in + 255) / 256);
     if (g.y > 65535u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cw_bits_ingest_packed_kernel, g, dim3(256), 0, s, (const uint64_t *)masks, (uint64_t *)T, slots, sh, input_slot0, n_in,

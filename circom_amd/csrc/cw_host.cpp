@@ -1794,6 +1794,12 @@ struct cw_batch {
     DevBuf<uint32_t> d_wslot;                         // witness position -> bit-table slot (sig_slot o w2s)
     DevBuf<uint32_t> d_fbinst;                        // instances of the side batch (device copy of fb_inst)
     const void *packed_in = nullptr;                  // cw_set_inputs_bits_device: uint64 masks [groups][n_inputs] instead of ext_in
+    // emitted-code batches ingest a 32-byte image in two steps (bits_run): cw_bits_ingest_kernel writes packed masks
+    // [groups][n_inputs] here in whole lines, the row writer moves them into the table.  The batch's own (never d_pmask, which holds
+    // what a caller set); allocated by set_input_source when the source becomes a 32-byte image, never inside cw_run (a captured
+    // path launches kernels only); null = the direct route (CW_BITS_INGEST_STAGED=0, or the allocation failed)
+    DevBuf<uint64_t> d_stage;
+    bool ingest_staged = false, stage_tried = false;
     DevBuf<uint32_t> d_erecs, d_wchunk, d_wterms, d_wctab, d_wrow;
     DevBuf<uint32_t> d_ichunk, d_iterms, d_itab, d_irow, d_sigslot;
     uint32_t n_ichunks = 0;
@@ -2340,6 +2346,13 @@ static void set_input_source(cw_batch *b, const void *ext, const void *packed, u
     if (complete) {
         b->all_set = true;
         std::fill(b->remaining.begin(), b->remaining.end(), 0);
+    }
+    // the staging masks of an emitted-code batch's 32-byte ingest (cw_batch::d_stage): here, once, because cw_run may be under
+    // capture.  A failed allocation is not an error: bits_run then stores into the table directly.
+    if (b->ingest_staged && !b->stage_tried && !packed && eb == 32 && b->device >= 0) {
+        b->stage_tried = true;
+        if (hipSetDevice(b->device) != hipSuccess || b->d_stage.alloc(std::max<size_t>((size_t)b->n_groups * b->c->n_inputs * 8, 8)) != hipSuccess)
+            (void)hipGetLastError();                      // (the launch wrappers report hipGetLastError: this failure is not theirs)
     }
 }
 static const void *input_image(const cw_batch *b) { return b->ext_in ? b->ext_in : b->d_in.get(); }
@@ -2943,6 +2956,10 @@ static int bits_batch_setup(cw_batch *b) {
         b->bits_sh = 5;
         b->bits_sigslot = &c->jit.sig_slot;
         b->n_groups_padded = (b->n_groups + 31) / 32 * 32;
+        // a 32-byte image reaches this table through staging masks and the whole-row writer (bits_run); CW_BITS_INGEST_STAGED=0
+        // keeps cw_bits_ingest_kernel's own scattered store (A/B timing of the two routes in one process)
+        b->ingest_staged = true;
+        if (const char *ev = getenv("CW_BITS_INGEST_STAGED")) b->ingest_staged = atoi(ev) != 0;
     } else {
         b->bits_slots = bp.n_slots;
         b->bits_sh = 0;
@@ -3022,7 +3039,12 @@ static int bits_run(cw_batch *b, const void *in) {
     HIPCHK(cwk_bits_init(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->n_groups_padded, b->d_fbmask, b->d_r1flag, b->d_status, b->d_first_bad, b->Bp));
     if (b->packed_in)
         HIPCHK(cwk_bits_ingest_packed(b->stream, b->packed_in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
-    else
+    else if (b->ingest_staged && b->d_stage) {
+        // the unchanged ingest kernel with the masks' own layout as its "table" (sh = 0, slots = n_inputs, slot 0: masks[g][k]):
+        // every wave's store is 512 contiguous bytes; then whole rows into the emitted code's table
+        HIPCHK(cwk_bits_ingest(b->stream, in, b->d_stage, c->n_inputs, 0, 0, c->n_inputs, b->batch, b->d_fbmask));
+        HIPCHK(cwk_bits_ingest_packed(b->stream, b->d_stage, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
+    } else
         HIPCHK(cwk_bits_ingest(b->stream, in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch, b->d_fbmask));
     TMARK(b, 1);
     if (b->jit) {

@@ -47,6 +47,9 @@ hipError_t cwk_bits_eval(hipStream_t s, const void *recs, const uint32_t *cmds, 
                          void *fbmask);
 hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t first,
                            uint32_t count, void *out);
+// packed masks[ceil(batch / 64)][n_in] -> the input slots of the table.  sh = 5: cw_bits_masks_to_table_rows_kernel writes whole
+// 256-byte rows, every chunk's 32 group columns (the padding groups of the last chunk get zeros); sh = 0: one mask per thread.
+// cwk_bits_ingest with (T = masks, slots = n_in, sh = 0, input_slot0 = 0) WRITES that form from a 32-byte image.
 hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                                   uint32_t batch);
 hipError_t cwk_bits_collect_inputs(hipStream_t s, const void *masks, const void *aos, const uint32_t *inst, uint32_t n_inst,

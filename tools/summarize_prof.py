@@ -56,7 +56,8 @@ if len(sys.argv) > 3:
         for k, v in tmp.items():
             dst[k] = sum(v) / len(v)
     def short_name(k):
-        if "ingest" in k:
+        # (an emitted-code batch ingests in two kernels: cw_bits_ingest_kernel into staging masks, then the whole-row writer)
+        if "ingest" in k or "masks_to_table_rows" in k:
             return "ingest"
         if "gather" in k:
             return "gather"
