@@ -16,6 +16,7 @@
 #include "cw_pieces.h"
 #include "cw_r1cs_products.h"
 #include "cw_columns.hip.h"
+#include "cw_list.hip.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
 #define GL_HALF (GL_P >> 1)
@@ -347,74 +348,39 @@ __global__ void __launch_bounds__(256) cw64_gather_kernel(const uint64_t *__rest
 //           only); 32-byte form: 16-byte pieces {value, 0} (even lanes) and {0, 0} (odd lanes), 1 KiB contiguous per store,
 //           two stores per row of the tile.  `out` must be 16-byte aligned in the 32-byte form.
 // Lanes past `count` and entries past n_wit neither read nor write.
-#define EG_T 64
-#define EG_S 65
-template <int EB>
-__global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit,
-                                                          uint32_t Bp, uint32_t first, uint32_t count, uint8_t *__restrict__ out) {
-    __shared__ uint64_t tile[EG_T * EG_S];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
-    const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
-    const uint64_t *Vj = V + first + j0 + lane;
-    uint64_t v[EG_T / 4];
-#pragma unroll
-    for (uint32_t i = 0; i < EG_T / 4; i++) {
-        const uint32_t k = wave + 4 * i;
-        const uint32_t slot = w2s[k < nk ? k0 + k : k0];             // always an entry of the list: the scalar load needs no branch
-        v[i] = k < nk && lane < nj ? Vj[(size_t)slot * Bp] : 0;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < EG_T / 4; i++) tile[(wave + 4 * i) * EG_S + lane] = v[i];
-    __syncthreads();
-    for (uint32_t j = wave; j < nj; j += 4) {
-        const size_t at = (size_t)(j0 + j) * n_wit + k0;             // first element of this row of the tile in `out`
-        if (EB == 8) {
-            if (lane < nk) ((uint64_t *)out)[at + lane] = tile[lane * EG_S + j];
-        } else {
-            uint4 *row = (uint4 *)out + at * 2;
-#pragma unroll
-            for (uint32_t h = 0; h < 2; h++) {
-                const uint32_t p = lane + 64 * h, k = p >> 1;
-                if (k < nk) {
-                    const uint64_t x = p & 1u ? 0 : tile[k * EG_S + j];
-                    row[p] = make_uint4((uint32_t)x, (uint32_t)(x >> 32), 0, 0);
-                }
-            }
-        }
-    }
-}
-
-// Egress by index (cw_get_witnesses_at*): out[j][k] = entry k of the range in instance idx[j].  The tile of the kernel above - 64
-// list positions x EG_T entries, rows of 65 words, the same conflict-free stage (nothing new in LDS) and the same 512-byte /
-// 1 KiB stores -, but lane l reads V[slot * Bp + idx[j0 + l]] instead of first + j0 + l: a vector load per lane, loaded once per
-// thread before the loop over the entries; for an ascending dense list the 64 addresses of a read are still one 512-byte run.
-//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list; with d_n the list ends
-//           at min(count, *d_n - pos0), read here (wave-uniform: a scalar load): a workgroup whose tile lies behind it leaves at
-//           once, before its barrier, and rows behind it are not written.
+//
+// AT: egress by index (cw_get_witnesses_at*): out[j][k] = entry k of the range in instance idx[j].  The same tile with list
+// positions for instances - the same stage (nothing new in LDS) and the same stores -, but lane l reads V[slot * Bp + idx[j0 + l]]
+// instead of first + j0 + l: a vector load per lane, loaded once per thread before the loop over the entries; for an ascending
+// dense list the 64 addresses of a read are still one 512-byte run.  `first` is not used.
+//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list, cut at *d_n
+//           (cw_list_limit): a workgroup whose tile lies behind the end leaves at once, before its barrier, and rows behind it
+//           are not written.
 //   bad     a position whose index is >= batch loads nothing and stages zeros: its row is zeros.  After a ballot one lane of the
 //           tile's first workgroup reports the lowest such position, pos0 + j0 + l, with atomicMin (`bad` may be nullptr; the
 //           caller fills it first).
-template <int EB>
-__global__ void __launch_bounds__(256) cw64_egress_at_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit,
-                                                             uint32_t Bp, uint32_t batch, const uint32_t *__restrict__ idx, uint32_t count,
-                                                             uint32_t pos0, const uint32_t *__restrict__ d_n, uint8_t *__restrict__ out,
-                                                             uint32_t *bad) {
+#define EG_T 64
+#define EG_S 65
+template <int EB, bool AT>
+__global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit,
+                                                          uint32_t Bp, uint32_t first, uint32_t count, uint8_t *__restrict__ out,
+                                                          uint32_t batch, const uint32_t *__restrict__ idx, uint32_t pos0,
+                                                          const uint32_t *__restrict__ d_n, uint32_t *bad) {
     __shared__ uint64_t tile[EG_T * EG_S];
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
-    uint32_t lim = count;
-    if (d_n) {
-        const uint32_t dn = *d_n, left = dn > pos0 ? dn - pos0 : 0u;
-        lim = left < lim ? left : lim;
-    }
-    if (j0 >= lim) return;                                             // the whole workgroup
+    const uint32_t lim = AT ? cw_list_limit(count, pos0, d_n) : count;
+    if (AT && j0 >= lim) return;                                       // the whole workgroup
     const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = lim - j0 < 64u ? lim - j0 : 64u;
-    const uint32_t inst = lane < nj ? idx[j0 + lane] : 0u;
-    const bool ok = lane < nj && inst < batch;
-    const uint64_t off = __ballot(lane < nj && !ok);
-    if (bad && off && blockIdx.x == 0 && threadIdx.x == 0) atomicMin(bad, pos0 + j0 + (uint32_t)__builtin_ctzll(off));
-    const uint64_t *Vj = V + (ok ? inst : 0u);
+    bool ok = lane < nj;
+    const uint64_t *Vj = V + first + j0 + lane;
+    if (AT) {
+        const uint32_t inst = ok ? idx[j0 + lane] : 0u;
+        const uint64_t off = __ballot(ok && inst >= batch);
+        if (bad && off && blockIdx.x == 0 && threadIdx.x == 0) atomicMin(bad, pos0 + j0 + (uint32_t)__builtin_ctzll(off));
+        ok = ok && inst < batch;
+        Vj = V + (ok ? inst : 0u);
+    }
     uint64_t v[EG_T / 4];
 #pragma unroll
     for (uint32_t i = 0; i < EG_T / 4; i++) {
@@ -788,33 +754,32 @@ hipError_t cwk64_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint3
         return hipGetLastError();
     });
 }
-// elem_bytes = 8 or 32; a launch holds at most 65 535 tiles of 64 instances (gridDim.y), larger counts are split as above
-hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
-                        void *out, uint32_t elem_bytes) {
+// The launches of cw64_egress_kernel: `count` instances from `first`, or (at) `count` positions of the list idx, cut at *d_n,
+// whose indices may name the instances below `batch`.  elem_bytes = 8 or 32 (32: `out` 16-byte aligned; a list also wants an
+// 8-byte image 8-byte aligned).  A launch holds at most 65 535 tiles of 64 instances or positions (gridDim.y), larger counts are
+// split as above; the entry tiles are gridDim.x, so n_wit is not limited.
+static hipError_t egress(bool at, hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                         void *out, uint32_t elem_bytes, uint32_t batch, const uint32_t *idx, const uint32_t *d_n, uint32_t *bad) {
     if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
     if (elem_bytes == 32 && ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+    if (at && (((uintptr_t)out & 7) || (((uintptr_t)idx | (uintptr_t)d_n | (uintptr_t)bad) & 3))) return hipErrorInvalidValue;
     if (!n_wit) return hipSuccess;
-    const auto kernel = elem_bytes == 8 ? cw64_egress_kernel<8> : cw64_egress_kernel<32>;
-    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t n) {
-        hipLaunchKernelGGL(kernel, dim3((n_wit + EG_T - 1) / EG_T, (n + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp,
-                           first + done, n, (uint8_t *)out + (size_t)done * n_wit * elem_bytes);
+    const auto kernel = at ? (elem_bytes == 8 ? cw64_egress_kernel<8, true> : cw64_egress_kernel<32, true>)
+                           : (elem_bytes == 8 ? cw64_egress_kernel<8, false> : cw64_egress_kernel<32, false>);
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + EG_T - 1) / EG_T, (m + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp,
+                           first + done, m, (uint8_t *)out + (size_t)done * n_wit * elem_bytes, batch, at ? idx + done : nullptr, done, d_n, bad);
         return hipGetLastError();
     });
 }
-// egress by index: elem_bytes = 8 or 32 (`out` 8- / 16-byte aligned); a launch holds at most 65 535 tiles of 64 list positions
-// (gridDim.y), a longer list is split as above.  `bad` (or nullptr) takes an atomicMin of the lowest position whose index is
-// >= batch; the caller fills it first.
+hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                        void *out, uint32_t elem_bytes) {
+    return egress(false, s, V, w2s, n_wit, Bp, first, count, out, elem_bytes, 0, nullptr, nullptr, nullptr);
+}
+// `bad` (or nullptr) takes an atomicMin of the lowest position whose index is >= batch; the caller fills it first.
 hipError_t cwk64_egress_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
                            uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t elem_bytes, uint32_t *d_bad) {
-    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
-    if (((uintptr_t)d_out & (elem_bytes == 32 ? 15 : 7)) || (((uintptr_t)d_idx | (uintptr_t)d_n_idx | (uintptr_t)d_bad) & 3)) return hipErrorInvalidValue;
-    if (!n_wit || !n_idx) return hipSuccess;
-    const auto kernel = elem_bytes == 8 ? cw64_egress_at_kernel<8> : cw64_egress_at_kernel<32>;
-    return cw_pieces(n_idx, 65535u * 64u, [&](uint32_t done, uint32_t m) {
-        hipLaunchKernelGGL(kernel, dim3((n_wit + EG_T - 1) / EG_T, (m + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp, batch,
-                           d_idx + done, m, done, d_n_idx, (uint8_t *)d_out + (size_t)done * n_wit * elem_bytes, d_bad);
-        return hipGetLastError();
-    });
+    return egress(true, s, V, w2s, n_wit, Bp, 0, n_idx, d_out, elem_bytes, batch, d_idx, d_n_idx, d_bad);
 }
 // packed rows of witness bits: instance tiles in gridDim.x, word tiles of 4 096 entries in gridDim.y: one launch.  `word` (or
 // nullptr) takes an atomicMin of report0 + j for every instance j of the launch that held a value > 1; the caller fills it first.

@@ -22,6 +22,7 @@
 #include "cw_pieces.h"
 #include "cw_r1cs_products.h"
 #include "fp256.hip.h"
+#include "cw_list.hip.h"
 
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -444,22 +445,42 @@ cw_bits_assert_kernel(const uint64_t *__restrict__ T, uint64_t slots, const uint
 // Round 5 (tools/ubench_egress.hip on the --O1 witness of the default line, 156 809 wires, profiles/r05n_ubench_egress*.txt; a
 // one-pass 16-byte fill of the same buffers writes 6.9 TB/s, hipMemsetAsync 6.7): streaming (nt) stores 4.29 TB/s -> plain
 // stores 4.7 - 4.8; 8 KiB instead of 4 KiB runs per wave 4.8 - 4.9; with 8 or more groups of 64 instances per launch the grid
-// walks the GROUPS fastest (the workgroups that run together then write the same elements of different instances): 5.1 - 5.8
+// walks the GROUPS fastest (`tiles_fastest`: the workgroups that run together then write the same elements of different instances): 5.1 - 5.8
 // for launches of 1 024 instances, 5.4 - 5.5 for 2 048 (elements fastest: 4.5 - 4.9); a sweep in pure address order (one
 // instance per workgroup, the mask words re-read from L2) 3.0, rotated starts 4.2 - 5.1, other workgroup sizes 4.6 - 4.8.
 #define BITS_GATHER_RUN 8      // consecutive 1 KiB pieces (32 elements each) a wave writes per instance: 8 KiB runs, 32 KiB per block
-__global__ void __launch_bounds__(256)
-cw_bits_gather_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n_wit,
-                      uint32_t first, uint32_t count, uint4 *__restrict__ out, uint32_t groups_fastest) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t bk = groups_fastest ? blockIdx.y : blockIdx.x, bj = groups_fastest ? blockIdx.x : blockIdx.y;
-    const uint32_t k0 = (bk * 4 + wv) * 32 * BITS_GATHER_RUN;               // this wave's elements
-    const uint32_t j0 = bj * 64;                                             // its 64 output instances
-    if (k0 >= n_wit) return;
-    const uint32_t i0 = first + j0, g = i0 >> 6, sh = i0 & 63u;
-    const bool two = sh && (uint64_t)(i0 + 64 - sh) < (uint64_t)first + count;
-    uint64_t win[BITS_GATHER_RUN];                                           // bit jj = the value in instance i0 + jj
-    bool have[BITS_GATHER_RUN];
+//
+// AT: egress by index (cw_get_witnesses_at*): out[j][k] (32 bytes) = witness element k of the range in instance idx[j].  The same
+// tile and stores - a wave owns 32 * BITS_GATHER_RUN elements x 64 list positions and writes whole 1 KiB runs of one position,
+// even lanes carrying the bit -, but the 64 positions of a tile may lie in 64 different groups, so there is no window to read:
+// the wave FORMS the 64-bit window of an element.  Lane l holds position j0 + l: its instance (loaded once, before the loop over
+// the elements), the address of its group (bits_group: both table layouts) and its bit number.  Per element the slot is a scalar
+// load (wslot[k], wave-uniform), every lane reads ITS group's word of that slot and a ballot of the lanes' bits is the window,
+// bit l = the value at position j0 + l; it is kept by the two lanes that write the element.  For an ascending dense list the 64
+// words of a read are one or two distinct addresses.  No LDS.  `first` is not used.
+//   dense   a tile whose live positions are all valid and name CONSECUTIVE instances (one ballot decides; what the tiles of an
+//           ascending dense list mostly are, the identity list always) has a window to read after all: the range form's read
+//           (bits_gather_window) from the tile's first instance - 8 loads per wave instead of 256 scalar loads, 256 vector loads
+//           and 256 ballots.
+//   grid    as above: with 8 or more tiles of positions per launch the grid walks the positions fastest (`tiles_fastest`).
+//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list, cut at *d_n
+//           (cw_list_limit); a wave whose tile lies behind the end leaves at once, rows behind it are not written.
+//   bad     a position whose index is >= batch reads nothing and contributes 0 to every ballot: its row is zeros.  One lane of
+//           the tile's first wave reports the lowest such position, pos0 + j0 + l, with atomicMin (`bad` may be nullptr; the
+//           caller fills it first).
+// The rows of the instances the side batch re-ran are written over afterwards (cw_kernels.hip cw_gather_many_kernel<., true>
+// with the instance -> side-batch map), in stream order.
+
+// The windows of a run of nj <= 64 consecutive instances from i0, all in the batch: one mask per lane pair (lane l: element
+// k0 + r * 32 + l / 2) from the group of i0, shifted down by sh = i0 % 64; the next group's OR-ed in above it when the run
+// crosses into that group, 64 - sh < nj (which is then a group of the batch).  A range tile is such a run from first + j0 with
+// nj = min(64, count - j0), a dense list tile one from its first instance: for the range, i0 + 64 - sh < first + count is the
+// same condition.
+__device__ __forceinline__ void bits_gather_window(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh,
+                                                   const uint32_t *__restrict__ wslot, uint32_t n_wit, uint32_t k0, uint32_t lane,
+                                                   uint32_t i0, uint32_t nj, uint64_t (&win)[BITS_GATHER_RUN], bool (&have)[BITS_GATHER_RUN]) {
+    const uint32_t g = i0 >> 6, sh = i0 & 63u;
+    const bool two = sh && 64u - sh < nj;
 #pragma unroll
     for (int r = 0; r < BITS_GATHER_RUN; r++) {
         const uint32_t k = k0 + r * 32 + (lane >> 1);
@@ -471,99 +492,55 @@ cw_bits_gather_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t l
             if (two) win[r] |= bits_group(T, slots, lsh, g + 1)[(size_t)sl << lsh] << (64 - sh);
         }
     }
-    const uint32_t nj = min(64u, count - j0);
-    const bool low_half = !(lane & 1);
-    uint4 *o = out + ((size_t)j0 * n_wit + k0) * 2 + lane;
-    for (uint32_t jj = 0; jj < nj; jj++) {
-#pragma unroll
-        for (int r = 0; r < BITS_GATHER_RUN; r++) {
-            const uint32_t bit = low_half ? (uint32_t)(win[r] >> jj) & 1u : 0u;
-            if (have[r]) o[r * 64] = make_uint4(bit, 0u, 0u, 0u);
-        }
-        o += (size_t)n_wit * 2;
-    }
 }
-
-// Egress by index (cw_get_witnesses_at*): out[j][k] (32 bytes) = witness element k of the range in instance idx[j].  The tile
-// and the stores of the kernel above - a wave owns 32 * BITS_GATHER_RUN elements x 64 list positions and writes whole 1 KiB runs
-// of one position, even lanes carrying the bit -, but the 64 positions of a tile may lie in 64 different groups, so there is no
-// window to read: the wave FORMS the 64-bit window of an element.  Lane l holds position j0 + l: its instance (loaded once, before
-// the loop over the elements), the address of its group (bits_group: both table layouts) and its bit number.  Per element the
-// slot is a scalar load (wslot[k], wave-uniform), every lane reads ITS group's word of that slot and a ballot of the lanes' bits
-// is the window, bit l = the value at position j0 + l; it is kept by the two lanes that write the element.  For an ascending
-// dense list the 64 words of a read are one or two distinct addresses.  No LDS.
-//   dense   a tile whose live positions are all valid and name CONSECUTIVE instances (one ballot decides; what the tiles of an
-//           ascending dense list mostly are, the identity list always) has a window to read after all: the kernel above's read -
-//           one mask per lane pair from the group of the first instance, shifted, the next group's OR-ed in when the run crosses
-//           into it - 8 loads per wave instead of 256 scalar loads, 256 vector loads and 256 ballots.
-//   grid    as above: with 8 or more tiles of positions per launch the grid walks the positions fastest (`tiles_fastest`).
-//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list; with d_n the list ends
-//           at min(count, *d_n - pos0), read here; a wave whose tile lies behind it leaves at once, rows behind it are not written.
-//   bad     a position whose index is >= batch reads nothing and contributes 0 to every ballot: its row is zeros.  One lane of
-//           the tile's first wave reports the lowest such position, pos0 + j0 + l, with atomicMin (`bad` may be nullptr; the
-//           caller fills it first).
-// The rows of the instances the side batch re-ran are written over afterwards (cw_kernels.hip cw_gather_at_kernel with the
-// instance -> side-batch map), in stream order.
+template <bool AT>
 __global__ void __launch_bounds__(256)
-cw_bits_gather_at_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n_wit,
-                         uint32_t batch, const uint32_t *__restrict__ idx, uint32_t count, uint32_t pos0, const uint32_t *__restrict__ d_n,
-                         uint4 *__restrict__ out, uint32_t *bad, uint32_t tiles_fastest) {
+cw_bits_gather_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n_wit,
+                      uint32_t first, uint32_t count, uint4 *__restrict__ out, uint32_t tiles_fastest, uint32_t batch,
+                      const uint32_t *__restrict__ idx, uint32_t pos0, const uint32_t *__restrict__ d_n, uint32_t *bad) {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t bk = tiles_fastest ? blockIdx.y : blockIdx.x, bj = tiles_fastest ? blockIdx.x : blockIdx.y;
     const uint32_t k0 = (bk * 4 + wv) * 32 * BITS_GATHER_RUN;               // this wave's elements
-    const uint32_t j0 = bj * 64;                                             // its 64 list positions
-    uint32_t lim = count;
-    if (d_n) {
-        const uint32_t dn = *d_n, left = dn > pos0 ? dn - pos0 : 0u;
-        lim = left < lim ? left : lim;
-    }
-    if (k0 >= n_wit || j0 >= lim) return;
+    const uint32_t j0 = bj * 64;                                             // its 64 output instances (list positions)
+    const uint32_t lim = AT ? cw_list_limit(count, pos0, d_n) : count;
+    if (k0 >= n_wit || (AT && j0 >= lim)) return;
     const uint32_t nj = min(64u, lim - j0);
-    const uint32_t inst = lane < nj ? idx[j0 + lane] : 0u;
-    const bool ok = lane < nj && inst < batch;
-    const uint64_t off = __ballot(lane < nj && !ok);
-    if (bad && off && k0 == 0 && lane == 0) atomicMin(bad, pos0 + j0 + (uint32_t)__builtin_ctzll(off));
-    const uint64_t *Tg = bits_group(T, slots, lsh, ok ? inst >> 6 : 0u);
-    const uint32_t bit_no = inst & 63u;
-    uint64_t win[BITS_GATHER_RUN];                                           // bit jj = the value at position j0 + jj
+    uint64_t win[BITS_GATHER_RUN];                                           // bit jj = the value in instance first + j0 + jj (at position j0 + jj)
     bool have[BITS_GATHER_RUN];
-    const uint32_t inst0 = __builtin_amdgcn_readfirstlane(inst);            // position j0 is always live
-    const bool dense = __ballot(lane < nj && (!ok || inst != inst0 + lane)) == 0;
-    if (dense) {
-        // instances inst0 .. inst0 + nj - 1, all < batch: the run crosses into group g + 1 when 64 - sh < nj, and that group exists
-        const uint32_t g = inst0 >> 6, sh = inst0 & 63u;
-        const bool two = sh && 64u - sh < nj;
+    if (!AT) {
+        bits_gather_window(T, slots, lsh, wslot, n_wit, k0, lane, first + j0, nj, win, have);
+    } else {
+        const uint32_t inst = lane < nj ? idx[j0 + lane] : 0u;
+        const bool ok = lane < nj && inst < batch;
+        const uint64_t off = __ballot(lane < nj && !ok);
+        if (bad && off && k0 == 0 && lane == 0) atomicMin(bad, pos0 + j0 + (uint32_t)__builtin_ctzll(off));
+        const uint64_t *Tg = bits_group(T, slots, lsh, ok ? inst >> 6 : 0u);
+        const uint32_t bit_no = inst & 63u;
+        const uint32_t inst0 = __builtin_amdgcn_readfirstlane(inst);        // position j0 is always live
+        const bool dense = __ballot(lane < nj && (!ok || inst != inst0 + lane)) == 0;
+        if (dense) {
+            bits_gather_window(T, slots, lsh, wslot, n_wit, k0, lane, inst0, nj, win, have);
+        } else
 #pragma unroll
         for (int r = 0; r < BITS_GATHER_RUN; r++) {
-            const uint32_t k = k0 + r * 32 + (lane >> 1);
-            have[r] = k < n_wit;
+            const uint32_t kr = k0 + r * 32;
+            have[r] = kr + (lane >> 1) < n_wit;
             win[r] = 0;
-            if (have[r]) {
-                const uint32_t sl = wslot[k];
-                win[r] = bits_group(T, slots, lsh, g)[(size_t)sl << lsh] >> sh;
-                if (two) win[r] |= bits_group(T, slots, lsh, g + 1)[(size_t)sl << lsh] << (64 - sh);
-            }
-        }
-    } else
+            // eight elements at a time: eight slots and eight words in flight before the first ballot.  An element past n_wit takes
+            // the slot of the run's first element (always an entry of the list); its window is kept by no lane that writes
+            for (uint32_t k8 = 0; k8 < 32 && kr + k8 < n_wit; k8 += 8) {
+                uint64_t word[8];
 #pragma unroll
-    for (int r = 0; r < BITS_GATHER_RUN; r++) {
-        const uint32_t kr = k0 + r * 32;
-        have[r] = kr + (lane >> 1) < n_wit;
-        win[r] = 0;
-        // eight elements at a time: eight slots and eight words in flight before the first ballot.  An element past n_wit takes
-        // the slot of the run's first element (always an entry of the list); its window is kept by no lane that writes
-        for (uint32_t k8 = 0; k8 < 32 && kr + k8 < n_wit; k8 += 8) {
-            uint64_t word[8];
+                for (uint32_t u = 0; u < 8; u++) {
+                    const uint32_t k = kr + k8 + u;
+                    const uint32_t sl = wslot[k < n_wit ? k : kr];           // wave-uniform
+                    word[u] = ok ? Tg[(size_t)sl << lsh] : 0;
+                }
 #pragma unroll
-            for (uint32_t u = 0; u < 8; u++) {
-                const uint32_t k = kr + k8 + u;
-                const uint32_t sl = wslot[k < n_wit ? k : kr];               // wave-uniform
-                word[u] = ok ? Tg[(size_t)sl << lsh] : 0;
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < 8; u++) {
-                const uint64_t m = __ballot((word[u] >> bit_no) & 1);
-                if ((lane >> 1) == k8 + u) win[r] = m;
+                for (uint32_t u = 0; u < 8; u++) {
+                    const uint64_t m = __ballot((word[u] >> bit_no) & 1);
+                    if ((lane >> 1) == k8 + u) win[r] = m;
+                }
             }
         }
     }
@@ -1105,33 +1082,33 @@ hipError_t cwk_bits_eval(hipStream_t s, const void *recs, const uint32_t *cmds, 
                            n_groups, (uint64_t *)fbmask);
     return hipGetLastError();
 }
-hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t first,
-                           uint32_t count, void *out) {
+// The launches of cw_bits_gather_kernel: `count` instances from `first`, or (at) `count` positions of the list idx, cut at *d_n,
+// whose indices may name the instances below `batch` (`out` 16-byte aligned).  Element blocks and tiles of 64 instances or
+// positions are the grid's two dimensions, the tiles fastest when a launch has 8 or more of them (see the kernel's comment);
+// 65 535 tiles per launch (the grid.y limit when the elements go first), a larger count in several launches, none behind one
+// that failed.
+static hipError_t bits_gather(bool at, hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit,
+                              uint32_t first, uint32_t count, void *out, uint32_t batch, const uint32_t *idx, const uint32_t *d_n, uint32_t *bad) {
     if (!count || !n_wit) return hipSuccess;
+    if (at && (((uintptr_t)out & 15) || (((uintptr_t)idx | (uintptr_t)d_n | (uintptr_t)bad) & 3))) return hipErrorInvalidValue;
     const uint32_t kblocks = (n_wit + 128 * BITS_GATHER_RUN - 1) / (128 * BITS_GATHER_RUN);
-    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t n) {   // grid.y limit; no launch behind one that failed
-        const uint32_t groups = (n + 63) / 64;
-        const uint32_t gf = groups >= 8 && kblocks <= 65535u;           // see the kernel's comment
-        hipLaunchKernelGGL(cw_bits_gather_kernel, gf ? dim3(groups, kblocks) : dim3(kblocks, groups), dim3(256), 0, s, (const uint64_t *)T, slots,
-                           sh, wslot, n_wit, first + done, n, (uint4 *)out + (size_t)done * n_wit * 2, gf);
+    const auto kernel = at ? cw_bits_gather_kernel<true> : cw_bits_gather_kernel<false>;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        const uint32_t tiles = (m + 63) / 64;
+        const uint32_t tf = tiles >= 8 && kblocks <= 65535u;
+        hipLaunchKernelGGL(kernel, tf ? dim3(tiles, kblocks) : dim3(kblocks, tiles), dim3(256), 0, s, (const uint64_t *)T, slots, sh, wslot,
+                           n_wit, first + done, m, (uint4 *)out + (size_t)done * n_wit * 2, tf, batch, at ? idx + done : nullptr, done, d_n, bad);
         return hipGetLastError();
     });
 }
-// egress by index from the bit table: element blocks in gridDim.x, tiles of 64 list positions in gridDim.y (65 535 per launch, a
-// longer list in several launches, none behind one that failed).  `bad` (or nullptr) takes an atomicMin of the lowest position
-// whose index is >= batch; the caller fills it first.
+hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t first,
+                           uint32_t count, void *out) {
+    return bits_gather(false, s, T, slots, sh, wslot, n_wit, first, count, out, 0, nullptr, nullptr, nullptr);
+}
+// `bad` (or nullptr) takes an atomicMin of the lowest position whose index is >= batch; the caller fills it first.
 hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t batch,
                               const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t *d_bad) {
-    if (!n_idx || !n_wit) return hipSuccess;
-    if (((uintptr_t)d_out & 15) || (((uintptr_t)d_idx | (uintptr_t)d_n_idx | (uintptr_t)d_bad) & 3)) return hipErrorInvalidValue;
-    const uint32_t kblocks = (n_wit + 128 * BITS_GATHER_RUN - 1) / (128 * BITS_GATHER_RUN);
-    return cw_pieces(n_idx, 65535u * 64u, [&](uint32_t done, uint32_t m) {
-        const uint32_t tiles = (m + 63) / 64;
-        const uint32_t tf = tiles >= 8 && kblocks <= 65535u;            // see cw_bits_gather_kernel's comment
-        hipLaunchKernelGGL(cw_bits_gather_at_kernel, tf ? dim3(tiles, kblocks) : dim3(kblocks, tiles), dim3(256), 0, s, (const uint64_t *)T, slots,
-                           sh, wslot, n_wit, batch, d_idx + done, m, done, d_n_idx, (uint4 *)d_out + (size_t)done * n_wit * 2, d_bad, tf);
-        return hipGetLastError();
-    });
+    return bits_gather(true, s, T, slots, sh, wslot, n_wit, 0, n_idx, d_out, batch, d_idx, d_n_idx, d_bad);
 }
 hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                                   uint32_t batch) {

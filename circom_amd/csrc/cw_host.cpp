@@ -3744,12 +3744,12 @@ extern "C" int cw_select_instances(cw_batch *b, uint32_t mask, uint32_t want, ui
 
 // Entries [skip, skip + n) of the witness list for the instances d_idx[0 .. min(n_idx, *d_n_idx)), [n_idx][n][eb] in DEVICE memory
 // at d_out, one kernel per table layout (cw_kernels.h), walking the engines as device_egress does:
-//   64-bit runtime     cw64_egress_at_kernel, both element sizes - also in the supplied-witness state
-//   bit-plane batches  cw_bits_gather_at_kernel on the bit table (it reports the bad positions), then ONE launch of
-//                      cw_gather_at_kernel on the side batch's table with the instance -> side-batch map writes over the rows of
+//   64-bit runtime     cw64_egress_kernel<EB, true>, both element sizes - also in the supplied-witness state
+//   bit-plane batches  cw_bits_gather_kernel<true> on the bit table (it reports the bad positions), then ONE launch of
+//                      cw_gather_many_kernel<MONT, true> on the side batch's table with the instance -> side-batch map writes over the rows of
 //                      the re-run instances - the host never learns the list; a side batch that holds the whole batch serves the
 //                      list alone.  The first egress after a cw_run waits for bits_resolve.
-//   256-bit schedule   cw_gather_at_kernel, canonical and Montgomery-form tables
+//   256-bit schedule   cw_gather_many_kernel<MONT, true>, canonical and Montgomery-form tables
 // `limit`: the instances an index may name - the batch's, also where a (possibly larger) side batch serves the list.
 static int at_egress(cw_batch *b, uint32_t limit, uint32_t skip, uint32_t n, const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx,
                      void *d_out, uint32_t eb, uint32_t *d_bad) {

@@ -99,7 +99,8 @@ hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, 
 //                     fbidx (instance -> position in the side batch or negative) and fbidx[i] in [0, n_fb), fbstatus[fbidx[i]].
 //                     Three launches (count, scan, scatter; no workgroup waits for another); `counts`: scratch of
 //                     cwsel::n_blocks(batch) words; d_idx == nullptr: *d_n only.
-//   cwk*_at           one kernel per table layout: d_out[j][k] = entry k of the range (wslot / w2s point at its first entry) of
+//   cwk*_at           the range egress kernel of each table layout with a list for the range (cwk_gather_many, cwk_bits_gather,
+//                     cwk64_egress: the AT = true instantiations, one launcher body per pair): d_out[j][k] = entry k of the range (wslot / w2s point at its first entry) of
 //                     instance d_idx[j], j < min(n_idx, *d_n_idx) (d_n_idx may be nullptr), canonical, 32 bytes (d_out 16-byte
 //                     aligned) or, cwk64_egress_at with elem_bytes = 8, 8 bytes (8-byte aligned).  A position whose index is
 //                     >= batch gets zeros and atomicMin(d_bad, position); d_bad may be nullptr, the caller fills it first.

@@ -13,6 +13,7 @@
 #include "cw_r1cs_products.h"
 #include "cw_select.h"
 #include "cw_columns.hip.h"
+#include "cw_list.hip.h"
 
 #define CW_BLOCK 256
 
@@ -970,7 +971,15 @@ cw_r1cs_staged_kernel(const uint4 *__restrict__ chunk, const uint2 *__restrict__
 }
 
 // ---- egress: one instance's witness as [n_witness][32 B] (getWitness + Fr_toLongNormal, main.cpp:326-332) ----
-// MONT: the table holds Montgomery forms: x~ -> x = mmul(x~, 1)   (the role of Fr_toLongNormal, generic/fr.cpp)
+// MONT: the table holds Montgomery forms: x~ -> x = mmul(x~, 1)   (the role of Fr_toLongNormal, generic/fr.cpp), on a value
+// held as the table's two halves
+__device__ __forceinline__ void fe_out_of_mont(uint4 &lo, uint4 &hi, const FpParams &P) {
+    fe x;
+    x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
+    x = fe_mmul(x, fe_small(1), P);
+    lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+    hi = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+}
 template <bool MONT>
 __global__ void __launch_bounds__(CW_BLOCK)
 cw_gather_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp,
@@ -979,13 +988,7 @@ cw_gather_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, 
     if (k >= n_wit) return;
     size_t base = (size_t)w2s[k] * 2 * Bp + instance;
     uint4 lo = V[base], hi = V[base + Bp];
-    if (MONT) {
-        fe x;
-        x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
-        x = fe_mmul(x, fe_small(1), P);
-        lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-        hi = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-    }
+    if (MONT) fe_out_of_mont(lo, hi, P);
     out[2 * (size_t)k] = lo;
     out[2 * (size_t)k + 1] = hi;
 }
@@ -999,24 +1002,65 @@ cw_gather_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, 
                           // tools/ubench_isa is 2.4 + 2.4); 8 -> 1.05 ms; 32 (66 KB, two blocks per CU) -> 1.19 ms; round 2's
                           // kernel (32, default-policy stores) 1.28 ms
 #endif
-template <bool MONT>
+// LDS: tile[element][half][instance] with rows of 65 uint4 (+1: bank spread).  The stage writes and the store loop reads 16-byte
+// words (ds_write_b128 / ds_read_b128).  Written with lane = instance: 64 consecutive uint4 of one row.  Read with lane =
+// (instance ii, piece): the lanes of a store instruction cover 64 / (2 GM_TILE) instances x 2 GM_TILE rows, word 65 * piece + ii -
+// with rows of 64 words every piece of an instance would start in the same bank.
+//
+// AT: egress by index (cw_get_witnesses_at*): out[j][k] = entry k of the range in instance idx[j].  The same tile with list
+// positions for instances, the same stage and stores; lane l reads column idx[i0 + l] of the table instead of first + i0 + l
+// (`first` is not used).  The index is loaded once per thread, before the loop over the entries.
+//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list, cut at *d_n
+//           (cw_list_limit): a workgroup whose tile lies behind the end leaves at once (before its barrier), rows behind it are
+//           not written.
+//   bad     a position whose index is >= batch loads nothing, stages zeros and gets a row of zeros; after a ballot one lane of
+//           the tile's first workgroup reports the lowest such position, pos0 + i0 + l, with atomicMin (`bad` may be nullptr; the
+//           caller fills it first).
+//   remap   with a table `remap` of n_remap entries the lane reads column remap[idx] of THIS table, and a position whose entry
+//           is negative (or whose index is >= n_remap) is LEFT ALONE: this is how the instances a bit-plane batch re-ran are
+//           written over from the side batch's table in one launch, behind cw_bits_gather_kernel<true> (which reports the bad
+//           ones).
+//   keep    keep[64] in LDS, one dword per list position, written by wave 0 (64 consecutive dwords: every bank at most once per
+//           group of 32 lanes) and read in the store loop: 64 / (2 GM_TILE) distinct addresses per instruction, the lanes that
+//           share one are served by a broadcast.  The range form never touches it and the compiler drops it there
+//           (33 280 bytes of LDS against 33 536).
+template <bool MONT, bool AT>
 __global__ void __launch_bounds__(256)
 cw_gather_many_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp,
-                      uint32_t first, uint32_t count, uint4 *__restrict__ out, FpParams P) {
-    __shared__ uint4 tile[GM_TILE][2][65];                          // [element][half][instance] (+1: bank spread)
+                      uint32_t first, uint32_t count, uint4 *__restrict__ out, FpParams P, uint32_t batch,
+                      const uint32_t *__restrict__ idx, uint32_t pos0, const uint32_t *__restrict__ d_n,
+                      const int32_t *__restrict__ remap, uint32_t n_remap, uint32_t *bad) {
+    __shared__ uint4 tile[GM_TILE][2][65];
+    __shared__ uint32_t keep[AT ? 64 : 1];
     const uint32_t k0 = blockIdx.x * GM_TILE, i0 = blockIdx.y * 64;
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;  // 4 waves
+    const uint32_t lim = AT ? cw_list_limit(count, pos0, d_n) : count;
+    if (AT && i0 >= lim) return;                                    // the whole workgroup
+    const bool live = i0 + lane < lim;
+    uint32_t inst = first + i0 + lane;
+    bool ok = live;
+    if (AT) {
+        inst = live ? idx[i0 + lane] : 0u;
+        if (remap) {
+            const int32_t r = live && inst < n_remap ? remap[inst] : -1;
+            ok = r >= 0 && (uint32_t)r < batch;
+            inst = (uint32_t)r;
+        } else {
+            ok = live && inst < batch;
+            const uint64_t off = __ballot(live && !ok);
+            if (bad && off && blockIdx.x == 0 && threadIdx.x == 0) atomicMin(bad, pos0 + i0 + (uint32_t)__builtin_ctzll(off));
+        }
+        if (wv == 0) keep[lane] = remap ? ok : live;
+    }
     for (uint32_t e = wv; e < GM_TILE; e += 4) {
         const uint32_t k = k0 + e;
-        if (k < n_wit && i0 + lane < count) {
-            const size_t base = (size_t)w2s[k] * 2 * Bp + first + i0 + lane;
-            uint4 lo = V[base], hi = V[base + Bp];
-            if (MONT) {
-                fe x;
-                x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
-                x = fe_mmul(x, fe_small(1), P);
-                lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-                hi = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+        if (k < n_wit && (AT || ok)) {                              // (a list stages zeros where it may not read)
+            uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+            if (ok) {
+                const size_t base = (size_t)w2s[k] * 2 * Bp + inst;
+                lo = V[base];
+                hi = V[base + Bp];
+                if (MONT) fe_out_of_mont(lo, hi, P);
             }
             tile[e][0][lane] = lo;
             tile[e][1][lane] = hi;
@@ -1029,86 +1073,7 @@ cw_gather_many_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ 
     const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
     for (uint32_t ii = wv * PER + sub; ii < 64; ii += 4 * PER) {
         const uint32_t k = k0 + e;
-        if (k < n_wit && i0 + ii < count) {
-            const uint4 v = tile[e][h][ii];
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            u32x4 w = {v.x, v.y, v.z, v.w};
-            __builtin_nontemporal_store(w, (u32x4 *)&out[((size_t)(i0 + ii) * n_wit + k) * 2 + h]);
-        }
-    }
-}
-
-// ---- egress by index (cw_get_witnesses_at*): out[j][k] = entry k of the range in instance idx[j] ---------------
-// cw_gather_many_kernel's tile (GM_TILE entries x 64 list positions, the same stage and the same 512-byte stores, conversion out
-// of Montgomery form per value); lane l reads column idx[i0 + l] of the table instead of first + i0 + l.  The index is loaded once
-// per thread, before the loop over the entries.
-//   length  `count` positions in this launch, the launch's first being position pos0 of the caller's list; with d_n the list ends
-//           at min(count, *d_n - pos0), read here: a workgroup whose tile lies behind it leaves at once (before its barrier),
-//           rows behind it are not written.
-//   bad     a position whose index is >= batch loads nothing, stages zeros and gets a row of zeros; after a ballot one lane of
-//           the tile's first workgroup reports the lowest such position, pos0 + i0 + l, with atomicMin (`bad` may be nullptr; the
-//           caller fills it first).
-//   remap   with a table `remap` of n_remap entries the lane reads column remap[idx] of THIS table, and a position whose entry
-//           is negative (or whose index is >= n_remap) is LEFT ALONE: this is how the instances a bit-plane batch re-ran are
-//           written over from the side batch's table in one launch, behind cw_bits_gather_at_kernel (which reports the bad ones).
-//   LDS     keep[64], one dword per list position, written by wave 0 (64 consecutive dwords: every bank at most once per group
-//           of 32 lanes) and read in the store loop, where the lanes of a store instruction cover 64 / (2 GM_TILE) positions:
-//           that many distinct addresses, the lanes that share one are served by a broadcast.  The tile itself is accessed as
-//           cw_gather_many_kernel accesses it (rows of 65 uint4).
-template <bool MONT>
-__global__ void __launch_bounds__(256)
-cw_gather_at_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch,
-                    const uint32_t *__restrict__ idx, uint32_t count, uint32_t pos0, const uint32_t *__restrict__ d_n,
-                    const int32_t *__restrict__ remap, uint32_t n_remap, uint4 *__restrict__ out, uint32_t *bad, FpParams P) {
-    __shared__ uint4 tile[GM_TILE][2][65];                          // [element][half][position] (+1: bank spread)
-    __shared__ uint32_t keep[64];
-    const uint32_t k0 = blockIdx.x * GM_TILE, i0 = blockIdx.y * 64;
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;  // 4 waves
-    uint32_t lim = count;
-    if (d_n) {
-        const uint32_t dn = *d_n, left = dn > pos0 ? dn - pos0 : 0u;
-        lim = left < lim ? left : lim;
-    }
-    if (i0 >= lim) return;                                          // the whole workgroup
-    const bool live = i0 + lane < lim;
-    uint32_t inst = live ? idx[i0 + lane] : 0u;
-    bool ok;
-    if (remap) {
-        const int32_t r = live && inst < n_remap ? remap[inst] : -1;
-        ok = r >= 0 && (uint32_t)r < batch;
-        inst = (uint32_t)r;
-    } else {
-        ok = live && inst < batch;
-        const uint64_t off = __ballot(live && !ok);
-        if (bad && off && blockIdx.x == 0 && threadIdx.x == 0) atomicMin(bad, pos0 + i0 + (uint32_t)__builtin_ctzll(off));
-    }
-    if (wv == 0) keep[lane] = remap ? ok : live;
-    for (uint32_t e = wv; e < GM_TILE; e += 4) {
-        const uint32_t k = k0 + e;
-        if (k < n_wit) {
-            uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
-            if (ok) {
-                const size_t base = (size_t)w2s[k] * 2 * Bp + inst;
-                lo = V[base];
-                hi = V[base + Bp];
-                if (MONT) {
-                    fe x;
-                    x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
-                    x = fe_mmul(x, fe_small(1), P);
-                    lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-                    hi = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-                }
-            }
-            tile[e][0][lane] = lo;
-            tile[e][1][lane] = hi;
-        }
-    }
-    __syncthreads();
-    constexpr uint32_t PIECES = 2 * GM_TILE, PER = 64 / PIECES;
-    const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
-    for (uint32_t ii = wv * PER + sub; ii < 64; ii += 4 * PER) {
-        const uint32_t k = k0 + e;
-        if (k < n_wit && keep[ii]) {
+        if (k < n_wit && (AT ? keep[ii] : i0 + ii < count)) {
             const uint4 v = tile[e][h][ii];
             typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             u32x4 w = {v.x, v.y, v.z, v.w};
@@ -1589,31 +1554,34 @@ hipError_t cwk_gather(hipStream_t s, const void *V, const uint32_t *w2s, uint32_
                            (uint4 *)out, P);
     return hipGetLastError();
 }
+// The launches of cw_gather_many_kernel: `count` instances from `first`, or (at) `count` positions of the list idx, cut at
+// *d_n, whose indices may name the instances below `batch` (`out` 16-byte aligned).  Entry tiles in gridDim.x, tiles of 64
+// instances or positions in gridDim.y - a launch holds at most 65 535 of those, a larger count goes in several launches
+// (cw_pieces.h), none behind one that failed.
+static hipError_t gather_many(bool at, hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
+                              uint32_t count, void *out, bool mont, const FpParams &P, uint32_t batch, const uint32_t *idx, const uint32_t *d_n,
+                              const int32_t *remap, uint32_t n_remap, uint32_t *bad) {
+    if (!count || !n_wit) return hipSuccess;
+    if (at && (((uintptr_t)out & 15) || (((uintptr_t)idx | (uintptr_t)d_n | (uintptr_t)bad) & 3))) return hipErrorInvalidValue;
+    const auto kernel = at ? (mont ? cw_gather_many_kernel<true, true> : cw_gather_many_kernel<false, true>)
+                           : (mont ? cw_gather_many_kernel<true, false> : cw_gather_many_kernel<false, false>);
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + GM_TILE - 1) / GM_TILE, (m + 63) / 64), dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp,
+                           first + done, m, (uint4 *)out + (size_t)done * n_wit * 2, P, batch, at ? idx + done : nullptr, done, d_n, remap,
+                           n_remap, bad);
+        return hipGetLastError();
+    });
+}
 hipError_t cwk_gather_many(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
                            uint32_t count, void *out, bool mont, const FpParams &P) {
-    if (!count || !n_wit) return hipSuccess;
-    dim3 g((n_wit + GM_TILE - 1) / GM_TILE, (count + 63) / 64);
-    if (mont)
-        hipLaunchKernelGGL(cw_gather_many_kernel<true>, g, dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp, first, count, (uint4 *)out, P);
-    else
-        hipLaunchKernelGGL(cw_gather_many_kernel<false>, g, dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp, first, count, (uint4 *)out, P);
-    return hipGetLastError();
+    return gather_many(false, s, V, w2s, n_wit, Bp, first, count, out, mont, P, 0, nullptr, nullptr, nullptr, 0, nullptr);
 }
-// egress by index from the 8 x u32 table: entry tiles in gridDim.x, tiles of 64 list positions in gridDim.y - a launch holds at
-// most 65 535 of those, a longer list goes in several launches (cw_pieces.h), none behind one that failed.  `bad` (or nullptr)
-// takes an atomicMin of the lowest position whose index is >= batch; the caller fills it first.  With `remap` the positions whose
-// remap entry is negative are left alone and nothing is reported.
+// `bad` (or nullptr) takes an atomicMin of the lowest position whose index is >= batch; the caller fills it first.  With `remap`
+// the positions whose remap entry is negative are left alone and nothing is reported.
 hipError_t cwk_gather_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
                          uint32_t n_idx, const uint32_t *d_n_idx, const int32_t *remap, uint32_t n_remap, void *d_out, uint32_t *d_bad,
                          bool mont, const FpParams &P) {
-    if (!n_idx || !n_wit) return hipSuccess;
-    if (((uintptr_t)d_out & 15) || (((uintptr_t)d_idx | (uintptr_t)d_n_idx | (uintptr_t)d_bad) & 3)) return hipErrorInvalidValue;
-    const auto kernel = mont ? cw_gather_at_kernel<true> : cw_gather_at_kernel<false>;
-    return cw_pieces(n_idx, 65535u * 64u, [&](uint32_t done, uint32_t m) {
-        hipLaunchKernelGGL(kernel, dim3((n_wit + GM_TILE - 1) / GM_TILE, (m + 63) / 64), dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp, batch,
-                           d_idx + done, m, done, d_n_idx, remap, n_remap, (uint4 *)d_out + (size_t)done * n_wit * 2, remap ? nullptr : d_bad, P);
-        return hipGetLastError();
-    });
+    return gather_many(true, s, V, w2s, n_wit, Bp, 0, n_idx, d_out, mont, P, batch, d_idx, d_n_idx, remap, n_remap, remap ? nullptr : d_bad);
 }
 hipError_t cwk_mulbench(hipStream_t s, const void *a, const void *b, void *out, uint32_t n, uint32_t iters,
                         const FpParams &P) {

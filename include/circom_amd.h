@@ -479,9 +479,9 @@ int cw_get_r1cs_products_device(cw_batch *b, uint32_t parts, uint32_t row0, uint
  *                it is made on first use and freed with the batch; a batch that never asks pays nothing.
  *   engines      select: csrc/cw_kernels.hip cw_select_block_kernel / cw_select_scan_kernel - count, scan, scatter as three
  *                launches, no workgroup waits for another - for every engine.  Egress: 64-bit runtime (csrc/cw64.hip
- *                cw64_egress_at_kernel, also in the supplied-witness state), 256-bit schedule (csrc/cw_kernels.hip
- *                cw_gather_at_kernel, canonical and Montgomery-form tables), bit-plane batches (csrc/cw_bits.hip
- *                cw_bits_gather_at_kernel, both table layouts; the rows of the instances the 256-bit side batch re-ran are written
+ *                cw64_egress_kernel<EB, true>, also in the supplied-witness state), 256-bit schedule (csrc/cw_kernels.hip
+ *                cw_gather_many_kernel<MONT, true>, canonical and Montgomery-form tables), bit-plane batches (csrc/cw_bits.hip
+ *                cw_bits_gather_kernel<true>, both table layouts; the rows of the instances the 256-bit side batch re-ran are written
  *                over from there in one launch).  The tiles and stores of the range kernels, the column taken from the list. */
 int cw_select_instances(cw_batch *b, uint32_t mask, uint32_t want, uint32_t *idx, uint32_t *n);
 int cw_select_instances_device(cw_batch *b, uint32_t mask, uint32_t want, void *d_idx, void *d_n);

@@ -1,15 +1,21 @@
 """Instance lists (include/circom_amd.h): cw_select_instances(_device) picks the instances whose status word satisfies
 (status & mask) == want, ascending, on the device; cw_get_witnesses_at(_device)(_n8) hands out the witnesses of a LIST of
 instances, out[j][k] = entry entry0 + k of instance idx[j].  Kernels: csrc/cw_kernels.hip cw_select_block_kernel /
-cw_select_scan_kernel (count, scan, scatter - three launches) and cw_gather_at_kernel, csrc/cw64.hip cw64_egress_at_kernel,
-csrc/cw_bits.hip cw_bits_gather_at_kernel.
+cw_select_scan_kernel (count, scan, scatter - three launches) and cw_gather_many_kernel<MONT, true>, csrc/cw64.hip cw64_egress_kernel<EB, true>,
+csrc/cw_bits.hip cw_bits_gather_kernel<true>.
 
 Expected values come from oracle.tape_eval (eval_flat, its failed flag, check_r1cs), never from another call into the library;
 agreement with np.flatnonzero((b.status() & mask) == want) is asserted as well.  The shapes: BitGadget(15) has 380 signals; the
 entry ranges (0, whole), (1, 7), (3, 65), (15, 17) are the edges of the 64-entry and 16-entry tiles (a witness of four entries
 clips them); batches of 65, 130 and 300 are one tile of 64 positions + 1, two + 2, four + 44; 2 049 instances are one count block
 of the select kernels and a block of one instance, 2 097 153 the smallest batch with a second pass of the scan's loop.  Device outputs are written
-into 0xA5 bytes that end at the end of an allocation."""
+into 0xA5 bytes that end at the end of an allocation.
+
+The egress by index is the AT = true instantiation of each table's range kernel (cw64_egress_kernel<EB, false>,
+cw_gather_many_kernel<MONT, false>, cw_bits_gather_kernel<false>), so a range and the list of its instances are compared byte for
+byte as well, both with the oracle: (first, count) = (0, 300) whole tiles and a last one of 44, (37, 201) and (63, 2) off a group
+boundary of the bit table (a shifted window that takes a second group, from both forms), (64, 64) exactly one tile, (299, 1) the
+last instance; 4 194 241 instances are the smallest range of the 8 x u32 table that takes a second launch."""
 import ctypes as C
 import functools
 import os
@@ -430,6 +436,111 @@ def test_gpu_bad_device_indices_give_zero_rows_and_are_reported(circuits, hip, m
             got, guard, word = hip.at(b, idx[:9], entry0, n, eb)
             assert word == NONE
     b.close()
+
+
+# ---- a range and the list of its instances: one kernel per table, the same bytes ---------------------------------------------------
+FORMS = [(0, 300), (37, 201), (63, 2), (64, 64), (299, 1)]                           # (first, count) of a batch of 300
+GUARD = 64
+
+
+def _guarded(hip, nbytes, call):
+    """`call(p)` writes an image of nbytes into 0xA5 bytes, GUARD more on either side: (image, the 2 x GUARD bytes around it)"""
+    p = hip.at_end(nbytes + 2 * GUARD) + GUARD
+    call(p)
+    return hip.download(p, nbytes), np.concatenate([hip.download(p - GUARD, GUARD), hip.download(p + nbytes, GUARD)])
+
+
+def _range_and_list(hip, b, want, first, count, nw, ebs):
+    """cw_get_witnesses_device(_n8) of [first, first + count), its entries [entry0, entry0 + n) against
+    cw_get_witnesses_at_device(_n8) of the list first .. first + count - 1 - and both against want[instance][entry][32]"""
+    idx = np.arange(first, first + count, dtype=np.uint32)
+    hip.put_list(idx)
+    for eb in ebs:
+        where = (first, count, eb)
+        ranged, guard = _guarded(hip, count * nw * eb, lambda p: (b.witnesses_device_n8 if eb == 8 else b.witnesses_device)(first, count, p))
+        ranged = ranged.reshape(count, nw, eb)
+        assert (guard == 0xA5).all(), ("range",) + where
+        assert (ranged == want[first:first + count, :, :eb]).all(), ("range",) + where
+        for entry0, n in (clip(e, m, nw) for e, m in RANGES):
+            hip.put(hip.word, np.array([0x12345678], dtype=np.uint32))
+            listed, guard = _guarded(hip, count * n * eb,
+                                     lambda p: b.witnesses_at_device(hip.list, count, p, entry0, n, d_bad=hip.word, n8=(eb == 8)))
+            assert (guard == 0xA5).all() and hip.words(hip.word, 1)[0] == NONE, ("list", entry0, n) + where
+            assert listed.tobytes() == ranged[:, entry0:entry0 + n].tobytes(), ("list", entry0, n) + where
+            assert (listed.reshape(count, n, eb) == want[first:first + count, entry0:entry0 + n, :eb]).all(), ("list", entry0, n) + where
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["interp", "jit", "wide", "gl"])
+def test_gpu_a_range_and_the_list_of_its_instances_are_the_same_bytes(circuits, hip, monkeypatch, kind):
+    """on the bit engines (37, 201) and (63, 2) start off a group boundary: the window read is shifted and takes a second group,
+    from the range form and from the dense branch of the list form"""
+    B = 300
+    c, b = _batch(circuits, monkeypatch, kind, B)
+    bits, want = _case(15, "goldilocks" if kind == "gl" else "bn128")
+    b.set_inputs_rows(pack_rows(bits[:B], (bits.shape[1] + 7) // 8, True))
+    b.run(); b.sync()
+    assert (b.status() == 0).all()
+    for first, count in FORMS:
+        _range_and_list(hip, b, want, first, count, c.n_witness, ebs=(32, 8) if kind == "gl" else (32,))
+    b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_a_range_and_its_list_convert_a_montgomery_table_alike(circuits, hip):
+    fc, c = circuits("m2mont")
+    assert c.montgomery and c.n_witness == 4
+    B = 300
+    rng = np.random.default_rng(300)
+    ins = [[int.from_bytes(rng.bytes(32), "little") % c.q for _ in range(2)] for _ in range(B)]
+    want = np.stack([_image(_eval(_flat("m2"), row)[0]) for row in ins])
+    b = c.batch(B)
+    b.set_inputs(ins)
+    b.run(); b.sync()
+    for first, count in FORMS:
+        _range_and_list(hip, b, want, first, count, 4, ebs=(32,))
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["interp", "jit"])
+def test_gpu_a_range_and_its_list_agree_on_the_rerun_instances(circuits, hip, monkeypatch, kind):
+    """instances 5, 64 and 129 are not boolean: the range form writes their rows over run by run (cw_rerun_runs), the list form in
+    one launch through the instance -> side-batch map"""
+    c, b = _batch(circuits, monkeypatch, kind, 130)
+    _, vals, want = _rerun_case()
+    _run_values(b, c, vals)
+    for first, count in ((0, 130), (37, 93), (63, 2), (64, 64), (129, 1), (5, 1)):
+        _range_and_list(hip, b, want, first, count, c.n_witness, ebs=(32,))
+    b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_a_range_of_more_than_65535_tiles_on_the_256_bit_schedule(circuits, hip):
+    """Multiplier2 on the 8 x u32 table (Montgomery form), 65 535 x 64 + 1 instances: the smallest batch whose range egress is a
+    second launch, of one instance.  Inputs below 2^31: the product is exact in 64 bits.  The image is half a gigabyte"""
+    fc, c = circuits("m2mont")
+    B = 65535 * 64 + 1
+    rng = np.random.default_rng(B)
+    ab = rng.integers(0, 1 << 31, size=(B, 2), dtype=np.uint32)
+    want = np.zeros((B, 4, 4), dtype=np.uint64)                  # the witness is (1, out, a, b)
+    want[:, 0, 0], want[:, 1, 0], want[:, 2:, 0] = 1, ab[:, 0].astype(np.uint64) * ab[:, 1], ab
+    b = c.batch(B)
+    b.set_inputs_range(0, ab)
+    b.run(); b.sync()
+    assert (b.status() == 0).all()
+    nbytes = B * 4 * 32
+    p = hip.alloc(nbytes + 2 * GUARD)
+    hip.h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    assert hip.h.hipMemset(p, 0xA5, nbytes + 2 * GUARD) == 0
+    b.witnesses_device(0, B, p + GUARD)
+    got = hip.download(p + GUARD, (B, 4, 4), np.uint64)
+    guard = np.concatenate([hip.download(p, GUARD), hip.download(p + GUARD + nbytes, GUARD)])
+    hip.h.hipFree(p)
+    b.close()
+    assert (guard == 0xA5).all()
+    bad = np.flatnonzero((got != want).any(axis=(1, 2)))
+    assert len(bad) == 0, "first rows that differ: %s" % bad[:8].tolist()
 
 
 # ---- select ----------------------------------------------------------------------------------------------------------------------
