@@ -64,10 +64,11 @@ __global__ void __launch_bounds__(256) cw_bits_init_kernel(uint64_t *T, uint64_t
 
 // ---- ingest: AoS canonical inputs [batch][n_in][32 B] -> one mask per (group, input) -----------------------------------
 // (setInputSignal's `signalValues[si] = val`, calcwit.cpp:93, for 64 instances at a time).  A workgroup of four waves handles
-// 256 consecutive inputs of one group: thread t owns input c * 256 + t and walks the 64 instances of the group, so every pair
-// of load instructions of a wave reads 2 KiB contiguous, the workgroup 8 KiB of one instance's 32 n_in-byte record; the thread
-// shifts the value's low bit into its own mask and keeps its own "not a bit" mask (values other than 0/1 flag their instance:
-// one atomicOr per offending thread, none in the loop); a wave's 64 masks leave as one store instruction.
+// 256 consecutive inputs of one group and walks the group's 64 instances: every pair of load instructions of a wave reads 2 KiB
+// contiguous, the workgroup 8 KiB of one instance's 32 n_in-byte record; the value's low bit is shifted into a mask per input,
+// beside it a "not a bit" mask (values other than 0/1 flag their instance: one atomicOr per offending lane, none in the loop).
+// In the first body (cw_bits_ingest_halves_kernel, below the kernel) thread t owns input c * 256 + t and a wave's 64 masks
+// leave as one store instruction; the table below is that body's.
 // Order matters more than the loop body (tools/ubench_ingest.hip, profiles/r05n_ubench_ingest*.txt, 137 GB of inputs; a
 // read-only uint4 sum of the same buffer reaches 6.45 TB/s on the same box):
 //   one wave per workgroup, groups fastest (rounds 3-5)                        24.2 ms   5.69 TB/s
@@ -76,7 +77,7 @@ __global__ void __launch_bounds__(256) cw_bits_init_kernel(uint64_t *T, uint64_t
 //   chunks of one group fastest                                                 28.3 ms: the waves that run together march through
 //                                                                               the 64 KB records of their groups in step
 //   chunks fastest + every group starts at its own instance (hash(g) & 63)      23.4 ms
-//   that, four waves per workgroup on consecutive chunks, unrolled x 4          22.2 ms   6.19 TB/s   <- this kernel
+//   that, four waves per workgroup on consecutive chunks, unrolled x 4          22.2 ms   6.19 TB/s   <- the walk of both bodies
 //   (two waves 22.6, eight 23.2, sixteen 23.3; unrolled x 2 22.9, x 8 22.5; no rotation 24.0-24.4)
 // Where the final store lands is the caller's choice of (T, slots, sh, input_slot0).  Into the interpreter's table (sh = 0) a
 // wave's store is 512 contiguous bytes.  Into the emitted code's table (sh = 5) its 64 lanes would hit 64 different 256-byte rows,
@@ -85,10 +86,151 @@ __global__ void __launch_bounds__(256) cw_bits_init_kernel(uint64_t *T, uint64_t
 // staging buffer of packed masks (cw_host.cpp bits_run: T = d_stage, slots = n_in, sh = 0, input_slot0 = 0, which IS
 // masks[group][k]) and cw_bits_masks_to_table_rows_kernel below writes the table from there in whole rows.  This kernel's source
 // and launch geometry are the same on both routes.
+//
+// HOW THE BYTES TRAVEL (tools/ubench_ingest.hip `ingest_line`, profiles/ingest_line_once_ubench.txt: three processes on the
+// 137.44 GB, every form checked against the same table and flag checksums; ms = average of six launches, per process):
+//   lane = one input, two 16-byte loads at a lane stride of 32 (the first body)     23.19  22.64  23.18   <- CW_BITS_INGEST_LINE=0
+//   lane = one 16-byte piece (below), plain loads                                    24.58  23.64  24.60
+//   the same, streaming (nt) loads                                                   21.88  21.57  21.83
+//   LDS-DMA into a ring of 4 KiB per wave, default policy                            23.93  22.99  23.95
+//   ... 8 KiB                                                                        23.97  23.09  23.99
+//   ... 16 KiB                                                                       23.27  22.67  23.25
+//   LDS-DMA, nt, ring of 4 KiB per wave                                              21.68  21.25  21.66
+//   LDS-DMA, nt, ring of 8 KiB per wave                                              21.64  21.50  21.64
+//   LDS-DMA, nt, ring of 16 KiB per wave                                             21.39  21.16  21.40   <- this kernel
+//   read only, same map: plain nt loads 19.84 / 20.12 / 19.86; LDS-DMA nt, 8 KiB 19.76 / 20.03 / 19.76 (6.83 - 6.96 TB/s)
+// That table is the tool's own layout (sh = 5, the direct route's scattered store), where the first body pays 1.0 - 1.5 ms for its
+// stores and this one does not.  With a group's masks contiguous (sh = 0: the staged route, the interpreter's table; part 2 of the
+// same file) the first body runs 21.68 / 21.91 / 22.08 and this kernel 21.32 / 22.00 / 21.80: inside the spread of the processes.
+// What decided is the library on the benchmark (profiles/ingest_line_once_parent_vs_new.json, three processes each, alternating):
+// table init + ingest + row writer 21.90 - 21.92 -> 21.45 - 21.47 ms, the step 32.69 - 32.72 -> 32.25 - 32.27 ms (+1.3 % witnesses/s
+// between the nearest runs, own ranges 0.08 %), the emitted kernel behind it 10.74 -> 10.75 ms; FETCH_SIZE of a launch
+// 138.04 GB = 1.0044 x the image -> 137.44 GB = 1.0000 x.  Building the masks by rotation (v_alignbit_b32, 7 instead of ~13 VALU
+// instructions per piece) changed nothing: the VALU work is not what separates the kernel from the read-only line.
+// With two loads of 16 bytes at a stride of 32 both instructions of a pair touch all 16 lines of the wave's 2 KiB run, half of each;
+// with eight loads per lane in flight a line can leave the L2 between its halves (the counters showed 1.04 x the image).  Here lane l
+// of load h takes piece 64 h + l of the run (cw_bits_layout.h line_*): one instruction = 1 KiB contiguous, a line belongs to one
+// instruction, so nothing is read twice and the streaming policy has nothing to lose: it is what moves the time (plain loads in
+// this map are slower than the old body).  Even lanes hold the low half of an input (its bit, and "more than 0 / 1"), odd lanes
+// the high half (any non-zero dword); one lane exchange after the loop ORs the odd lane's flags into its even neighbour's, the
+// even lanes store (32 masks = 256 contiguous bytes per instruction when sh = 0) and raise fbmask.  No cross-lane operation in the loop.
+//
+// The ring: a wave owns BITS_LINE_RING slots of 1 KiB of LDS; load n = 2 ii + h lands in slot n % BITS_LINE_RING, lane l's piece at
+// byte 16 l, and the lane that asked reads it back (ds_read_b128 at slot * 1024 + 16 l: no transposition).  Bank arithmetic of
+// the read-back: ds_read_b128 is served in four groups of 16 consecutive lanes; a group reads 256 consecutive bytes = dwords
+// 64 q .. 64 q + 63 of the slot, every one of the 64 banks exactly once: no conflict (by the documented bank rules; no counter
+// pass was taken).  hipcc neither sees the asm reads nor orders the DMA against them, so the waits are ours
+// (cw_bits_layout.h line_ring_*): the wave works in batches of BITS_LINE_RING / 2 loads; `s_waitcnt vmcnt(P)` ahead of a batch's
+// reads, P = line_ring_pending = the loads issued BEHIND the batch (the wave issues no other vector memory operation inside the
+// loop: the stores and the atomic come after it; loads return in order); `s_waitcnt lgkmcnt(0)` after the reads and ahead of
+// the DMAs that re-target their slots.  Checked in the disassembly: each group of ds_read_b128 follows its vmcnt, no
+// global_load_lds of a slot stands between that slot's read and the lgkmcnt(0), nothing touches a read's registers before it.
+// 16 slots = 16 KiB per wave, 64 KiB per workgroup: two workgroups per CU, 2 waves per SIMD, 32 loads of 1 KiB in flight per SIMD.
+// A ragged last group (fewer than 64 instances) walks its instances in order with plain loads of the same map.
+// kernel-resource-usage (gfx950):   old body  50 VGPRs, 35 SGPRs, no LDS, 8 waves per SIMD, no scratch
+//                                   this      112 VGPRs, 98 SGPRs, 65 536 bytes of LDS, 2 waves per SIMD (the LDS decides), no scratch
 #define BITS_INGEST_WAVES 4
+#define BITS_LINE_RING 16
+static_assert(BITS_INGEST_WAVES == cwlayout::LINE_WAVES, "the workgroup of both ingest bodies");
+struct BitsLineAcc {
+    uint64_t bit[2], bad[2];
+    uint32_t thr;                                                    // even lanes (low halves) 1, odd lanes 0: cwlayout::line_bad
+    __device__ __forceinline__ void take(int h, const u32x4 v, uint32_t inst) {
+        bit[h] |= (uint64_t)(v.x & 1u) << inst;
+        bad[h] |= (uint64_t)((uint32_t)(v.x > thr) | (uint32_t)((v.y | v.z | v.w) != 0u)) << inst;
+    }
+};
+__device__ __forceinline__ void bits_line_dma(const uint4 *src, uint32_t lds_byte) {          // 64 lanes x 16 bytes -> lds_byte + 16 lane, nt
+    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)(uintptr_t)lds_byte,
+                                     16, 0, 2);
+}
+// batch b of the ring: wait until at most PENDING of the wave's loads are in flight, read the batch's slots, wait for the reads,
+// hand the slots to the loads BITS_LINE_RING further on, then use what was read
+template <int PENDING, bool REFILL, int HALF>
+__device__ __forceinline__ void bits_line_batch(uint32_t b, BitsLineAcc &A, const uint4 *base, size_t step, const uint32_t (&o)[2], uint32_t r,
+                                                uint32_t ring, uint32_t lane16) {
+    constexpr int D = BITS_LINE_RING, BT = (int)cwlayout::line_ring_batch(D);
+    u32x4 v[BT];
+    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PENDING) : "memory");
+#pragma unroll
+    for (int j = 0; j < BT; j++)
+        asm volatile("ds_read_b128 %0, %1" : "=v"(v[j]) : "v"(ring + cwlayout::line_ring_byte(HALF * BT + j, 0) + lane16));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < BT; j++) asm volatile("" : "+v"(v[j]));     // nothing uses a read's registers above the wait
+    if (REFILL) {
+#pragma unroll
+        for (int j = 0; j < BT; j++) {
+            const uint32_t n = b * BT + j + D;
+            bits_line_dma(base + cwlayout::line_instance(n >> 1, r) * step + o[j & 1], ring + cwlayout::line_ring_byte(HALF * BT + j, 0));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < BT; j++) A.take(j & 1, v[j], cwlayout::line_instance((b * BT + j) >> 1, r));
+}
 __global__ void __launch_bounds__(64 * BITS_INGEST_WAVES)
 cw_bits_ingest_kernel(const uint4 *__restrict__ in, uint64_t *__restrict__ T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                       uint32_t batch, uint64_t *fbmask, uint32_t n_chunks) {
+    using namespace cwlayout;
+    constexpr uint32_t D = BITS_LINE_RING, BT = line_ring_batch(D), NB = LINE_RING_LOADS / BT;
+    static_assert(D % 4 == 0 && LINE_RING_LOADS % D == 0 && NB % 2 == 0 && NB >= 4, "whole rounds of the ring; both loads of an instance in one batch");
+    static_assert(line_ring_pending(D, 0) == BT && line_ring_pending(D, NB - 3) == BT && line_ring_refills(D, NB - 3), "steady state");
+    static_assert(line_ring_pending(D, NB - 2) == BT && !line_ring_refills(D, NB - 2), "the last batch but one");
+    static_assert(line_ring_pending(D, NB - 1) == 0 && !line_ring_refills(D, NB - 1), "the last batch");
+    __shared__ uint4 ring_lds[BITS_INGEST_WAVES * D * (LINE_SLOT_BYTES / 16)];
+    const uint32_t c = blockIdx.x % n_chunks, g = blockIdx.x / n_chunks;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = line_wave_input0(c, wave);
+    if (k0 >= n_in) return;                                          // the whole wave; no barrier below
+    const uint32_t i0 = g * 64, ni = min(64u, batch - i0);
+    const uint32_t p[2] = {line_piece(k0, 0, lane), line_piece(k0, 1, lane)};
+    const bool act[2] = {line_piece_active(p[0], n_in), line_piece_active(p[1], n_in)};
+    // an inactive lane reads the wave's first piece again (valid memory, a line the wave reads anyway) and drops it at the end
+    const uint32_t o[2] = {act[0] ? p[0] : 2u * k0, act[1] ? p[1] : 2u * k0};
+    const uint4 *base = in + (size_t)i0 * n_in * 2;
+    const size_t step = (size_t)n_in * 2;
+    BitsLineAcc A;
+    A.bit[0] = A.bit[1] = A.bad[0] = A.bad[1] = 0;
+    A.thr = line_piece_half(lane) ? 0u : 1u;
+    if (ni == 64) {
+        const uint32_t r = line_group_start(g);
+        const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4 *)ring_lds + wave * (D * LINE_SLOT_BYTES);
+        const uint32_t lane16 = line_ring_byte(0, lane);
+#pragma unroll
+        for (uint32_t n = 0; n < D; n++) bits_line_dma(base + line_instance(n >> 1, r) * step + o[n & 1], ring + line_ring_byte(line_ring_slot(n, D), 0));
+        for (uint32_t b = 0; b + 2 < NB; b += 2) {
+            bits_line_batch<BT, true, 0>(b, A, base, step, o, r, ring, lane16);
+            bits_line_batch<BT, true, 1>(b + 1, A, base, step, o, r, ring, lane16);
+        }
+        bits_line_batch<BT, false, 0>(NB - 2, A, base, step, o, r, ring, lane16);
+        bits_line_batch<0, false, 1>(NB - 1, A, base, step, o, r, ring, lane16);
+    } else {
+        const uint4 *q = base;
+        for (uint32_t ii = 0; ii < ni; ii++) {
+            const u32x4 v0 = *(const u32x4 *)(q + o[0]), v1 = *(const u32x4 *)(q + o[1]);
+            q += step;
+            A.take(0, v0, ii);
+            A.take(1, v1, ii);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        if (!act[h]) A.bit[h] = A.bad[h] = 0;
+        A.bad[h] |= (uint64_t)__shfl_xor((unsigned long long)A.bad[h], 1);        // the odd lane holds the other half of the same input
+    }
+    if (!line_piece_half(lane)) {
+        uint64_t *Tg = bits_group(T, slots, sh, g);
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+            if (act[h]) Tg[(size_t)(input_slot0 + line_piece_input(p[h])) << sh] = A.bit[h];
+        const uint64_t bad = A.bad[0] | A.bad[1];
+        if (bad) atomicOr((unsigned long long *)&fbmask[g], (unsigned long long)bad);
+    }
+}
+// the parent's body (CW_BITS_INGEST_LINE=0): lane = one input, two 16-byte loads at a lane stride of 32
+__global__ void __launch_bounds__(64 * BITS_INGEST_WAVES)
+cw_bits_ingest_halves_kernel(const uint4 *__restrict__ in, uint64_t *__restrict__ T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
+                             uint32_t batch, uint64_t *fbmask, uint32_t n_chunks) {
     const uint32_t c = blockIdx.x % n_chunks, g = blockIdx.x / n_chunks;
     const uint32_t k = c * (64 * BITS_INGEST_WAVES) + threadIdx.x;
     if (k >= n_in) return;                                           // no cross-lane operation below
@@ -1058,15 +1200,24 @@ hipError_t cwk_bits_init(hipStream_t s, void *T, uint64_t slots, uint32_t sh, ui
                        (uint64_t *)fbmask, (uint64_t *)r1flag, status, first_bad, Bp);
     return hipGetLastError();
 }
-hipError_t cwk_bits_ingest(hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
-                           uint32_t batch, void *fbmask) {
+template <class K>
+static hipError_t bits_ingest_launch(K kernel, hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
+                                     uint32_t batch, void *fbmask) {
     if (n_in == 0 || batch == 0) return hipSuccess;
     const uint32_t per = 64 * BITS_INGEST_WAVES, n_chunks = (n_in + per - 1) / per;
     const uint64_t blocks = (uint64_t)((batch + 63) / 64) * n_chunks;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cw_bits_ingest_kernel, dim3((uint32_t)blocks), dim3(per), 0, s, (const uint4 *)in, (uint64_t *)T, slots, sh, input_slot0, n_in,
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(per), 0, s, (const uint4 *)in, (uint64_t *)T, slots, sh, input_slot0, n_in,
                        batch, (uint64_t *)fbmask, n_chunks);
     return hipGetLastError();
+}
+hipError_t cwk_bits_ingest(hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
+                           uint32_t batch, void *fbmask) {
+    return bits_ingest_launch(cw_bits_ingest_kernel, s, in, T, slots, sh, input_slot0, n_in, batch, fbmask);
+}
+hipError_t cwk_bits_ingest_halves(hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
+                                  uint32_t batch, void *fbmask) {
+    return bits_ingest_launch(cw_bits_ingest_halves_kernel, s, in, T, slots, sh, input_slot0, n_in, batch, fbmask);
 }
 hipError_t cwk_bits_eval(hipStream_t s, const void *recs, const uint32_t *cmds, uint32_t n_batches, uint32_t ring, uint32_t cache,
                          void *T, uint64_t slots, uint32_t n_groups, uint32_t width, const uint32_t *aslots, uint32_t n_asserts,

@@ -1800,6 +1800,7 @@ struct cw_batch {
     // path launches kernels only); null = the direct route (CW_BITS_INGEST_STAGED=0, or the allocation failed)
     DevBuf<uint64_t> d_stage;
     bool ingest_staged = false, stage_tried = false;
+    bool ingest_line = true;                          // CW_BITS_INGEST_LINE=0: the previous body of the ingest kernel (cwk_bits_ingest_halves), both routes
     DevBuf<uint32_t> d_erecs, d_wchunk, d_wterms, d_wctab, d_wrow;
     DevBuf<uint32_t> d_ichunk, d_iterms, d_itab, d_irow, d_sigslot;
     uint32_t n_ichunks = 0;
@@ -2949,6 +2950,9 @@ static int bits_batch_setup(cw_batch *b) {
     // and is then bound by the table's bytes: it wins from a few hundred thousand instances.  CW_BITS_JIT = 0 / 1 overrides.
     b->jit = c->has_jit && b->batch >= cwbits::JIT_MIN_BATCH;
     if (const char *ev = getenv("CW_BITS_JIT")) b->jit = c->has_jit && atoi(ev) != 0;
+    // the ingest kernel's body (cw_bits.hip: every line by one streaming LDS-DMA load / the two-halves loads), read once here like
+    // CW_BITS_INGEST_STAGED: A/B timing of the two bodies in one process
+    if (const char *ev = getenv("CW_BITS_INGEST_LINE")) b->ingest_line = atoi(ev) != 0;
     if (b->jit) {
         hipError_t e1 = module_for_device(c->jit_mod, b->device, c->jit.code, cwbits::JIT_KERNEL, &b->jit_fn);
         if (e1 != hipSuccess) return fail(CW_EDEVICE, std::string("loading the emitted bit-plane code failed: ") + hipGetErrorString(e1));
@@ -3040,12 +3044,12 @@ static int bits_run(cw_batch *b, const void *in) {
     if (b->packed_in)
         HIPCHK(cwk_bits_ingest_packed(b->stream, b->packed_in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
     else if (b->ingest_staged && b->d_stage) {
-        // the unchanged ingest kernel with the masks' own layout as its "table" (sh = 0, slots = n_inputs, slot 0: masks[g][k]):
-        // every wave's store is 512 contiguous bytes; then whole rows into the emitted code's table
-        HIPCHK(cwk_bits_ingest(b->stream, in, b->d_stage, c->n_inputs, 0, 0, c->n_inputs, b->batch, b->d_fbmask));
+        // the ingest kernel with the masks' own layout as its "table" (sh = 0, slots = n_inputs, slot 0: masks[g][k]): a wave's stores
+        // are contiguous runs of masks; then whole rows into the emitted code's table
+        HIPCHK((b->ingest_line ? cwk_bits_ingest : cwk_bits_ingest_halves)(b->stream, in, b->d_stage, c->n_inputs, 0, 0, c->n_inputs, b->batch, b->d_fbmask));
         HIPCHK(cwk_bits_ingest_packed(b->stream, b->d_stage, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch));
     } else
-        HIPCHK(cwk_bits_ingest(b->stream, in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch, b->d_fbmask));
+        HIPCHK((b->ingest_line ? cwk_bits_ingest : cwk_bits_ingest_halves)(b->stream, in, b->d_T, b->bits_slots, b->bits_sh, cwbits::IN_BASE, c->n_inputs, b->batch, b->d_fbmask));
     TMARK(b, 1);
     if (b->jit) {
         // one wave per chunk of 2 048 instances runs the circuit's emitted code: gates on registers, every signal value stored

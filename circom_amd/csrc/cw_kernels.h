@@ -42,6 +42,9 @@ hipError_t cwk_bits_init(hipStream_t s, void *T, uint64_t slots, uint32_t sh, ui
                          uint32_t *status, uint32_t *first_bad, uint32_t Bp);
 hipError_t cwk_bits_ingest(hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                            uint32_t batch, void *fbmask);
+// the same result by the previous body (two 16-byte loads per lane and input; CW_BITS_INGEST_LINE=0: A/B timing in one process)
+hipError_t cwk_bits_ingest_halves(hipStream_t s, const void *in, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
+                                  uint32_t batch, void *fbmask);
 hipError_t cwk_bits_eval(hipStream_t s, const void *recs, const uint32_t *cmds, uint32_t n_batches, uint32_t ring, uint32_t cache,
                          void *T, uint64_t slots, uint32_t n_groups, uint32_t width, const uint32_t *aslots, uint32_t n_asserts,
                          void *fbmask);
