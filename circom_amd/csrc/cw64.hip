@@ -17,6 +17,7 @@
 #include "cw_r1cs_products.h"
 #include "cw_columns.hip.h"
 #include "cw_list.hip.h"
+#include "cw_wtns_digest.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
 #define GL_HALF (GL_P >> 1)
@@ -808,4 +809,39 @@ hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, 
                            (uint64_t *)d_out + off);
         return hipGetLastError();
     });
+}
+
+// ---- witness digests (cw_get_wtns_digests*, cw_wtns_digest.h) ----------------------------------------------------------------
+// SHA-256 of the .wtns file of every instance, n8 = 8: lane = instance, a wave owns the table group (first >> 6) + blockIdx.x and
+// walks the message with cwdig::walk - 8 elements per block, V[w2s[k]][instance], the slot a scalar load, 512 contiguous bytes per
+// wave and element; the eight elements of block j + 1 are requested before the rounds of block j.  Also served in the
+// supplied-witness state.  Lanes outside [first, first + count) read the padded table (Bp is a multiple of 256) and store nothing.
+struct Digest64Src {
+    static constexpr uint32_t EW = 2, H = 13, RUN = 1;
+    typedef uint64_t Raw;
+    const uint64_t *__restrict__ Vj;                      // column of the lane's instance
+    const uint32_t *__restrict__ w2s;
+    uint32_t Bp;
+    __device__ __forceinline__ Raw fetch(uint32_t k) const { return Vj[(size_t)w2s[k] * Bp]; }
+    __device__ __forceinline__ void words(const Raw &r, uint32_t w[2]) const {
+        w[0] = (uint32_t)r;
+        w[1] = (uint32_t)(r >> 32);
+    }
+};
+__global__ void __launch_bounds__(64) cw64_wtns_digest_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t Bp,
+                                                              uint32_t first, uint32_t count, uint4 *__restrict__ out, cwdig::Plan plan) {
+    const uint32_t inst = cwdig::wave_group(first, blockIdx.x) * 64u + threadIdx.x;
+    Digest64Src src{V + inst, w2s, Bp};
+    uint32_t st[8];
+    cwdig::walk(plan, src, st);
+    cwdig::store_digest(out, first, count, inst, st);
+}
+// digests [count][32] of the instances [first, first + count): one wave per table group of the range; d_out 16-byte aligned
+hipError_t cwk64_wtns_digest(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t Bp, uint32_t first, uint32_t count, void *d_out,
+                             const cwdig::Plan &plan) {
+    if (count == 0) return hipSuccess;
+    if (((uintptr_t)d_out & 15) || plan.n8 != 8 || plan.n_witness == 0 || (uint64_t)first + count > Bp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cw64_wtns_digest_kernel, dim3(cwdig::n_groups(first, count)), dim3(64), 0, s, (const uint64_t *)V, w2s, Bp, first, count,
+                       (uint4 *)d_out, plan);
+    return hipGetLastError();
 }

@@ -23,6 +23,7 @@
 #include "cw_r1cs_products.h"
 #include "fp256.hip.h"
 #include "cw_list.hip.h"
+#include "cw_wtns_digest.h"
 
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -1362,5 +1363,49 @@ hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, co
         hipLaunchKernelGGL(cw_bits_r1cs_wide_kernel, g, dim3(64), 0, s, (const uint4 *)chunk, n_chunks, (const uint2 *)terms, ctab,
                            row_orig, (const uint64_t *)T, slots, sh, onl, n_groups, batch, status, first_bad, P);
     }
+    return hipGetLastError();
+}
+
+// ---- witness digests (cw_get_wtns_digests*, cw_wtns_digest.h) ----------------------------------------------------------------
+// SHA-256 of the .wtns file of every instance of a bit table (n8 = 32, both layouts): lane = instance, a wave owns the table
+// group (first >> 6) + blockIdx.x and walks the message with cwdig::walk.  The 64 instances' bits of an entry are ONE 8-byte
+// word, at the address cw_get_signal computes; group and slot are wave-uniform (readfirstlane), so the word is a scalar load and
+// the lane's element is (mask >> lane) & 1 in byte 0 of 32.  The load of the mask depends on the load of the slot: both are
+// fetched for a run of RUN = 4 blocks (8 entries) at a time - the eight slots, then the eight masks - a run ahead of the rounds,
+// so that this latency is paid once per run, not inside every block.  The instances the side batch re-ran are written over by the
+// host's walk (cw_host.cpp digest_egress).
+struct DigestBitsSrc {
+    static constexpr uint32_t EW = 8, H = 19, RUN = 4;
+    typedef uint64_t Raw;                                 // the mask of the entry: wave-uniform
+    const uint64_t *__restrict__ Tg;                      // the group's slots, (1 << lsh) words apart
+    const uint32_t *__restrict__ wslot;
+    uint32_t lsh, lane;
+    __device__ __forceinline__ Raw fetch(uint32_t k) const {
+        const uint32_t sl = __builtin_amdgcn_readfirstlane(wslot[k]);
+        return Tg[(size_t)sl << lsh];
+    }
+    __device__ __forceinline__ void words(const Raw &m, uint32_t w[8]) const {
+        w[0] = (uint32_t)(m >> lane) & 1u;
+#pragma unroll
+        for (int i = 1; i < 8; i++) w[i] = 0;
+    }
+};
+__global__ void __launch_bounds__(64)
+cw_bits_wtns_digest_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t first,
+                           uint32_t count, uint4 *__restrict__ out, cwdig::Plan plan) {
+    const uint32_t g = cwdig::wave_group(first, blockIdx.x);
+    DigestBitsSrc src{bits_group(T, slots, lsh, g), wslot, lsh, threadIdx.x};
+    uint32_t st[8];
+    cwdig::walk(plan, src, st);
+    cwdig::store_digest(out, first, count, g * 64u + threadIdx.x, st);
+}
+// digests [count][32] of the instances [first, first + count) as the bit table holds them: one wave per table group of the range
+// (every group of the range exists: first + count <= batch); d_out 16-byte aligned
+hipError_t cwk_bits_wtns_digest(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t first, uint32_t count,
+                                void *d_out, const cwdig::Plan &plan) {
+    if (count == 0) return hipSuccess;
+    if (((uintptr_t)d_out & 15) || plan.n8 != 32 || plan.n_witness == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cw_bits_wtns_digest_kernel, dim3(cwdig::n_groups(first, count)), dim3(64), 0, s, (const uint64_t *)T, slots, sh, wslot,
+                       first, count, (uint4 *)d_out, plan);
     return hipGetLastError();
 }

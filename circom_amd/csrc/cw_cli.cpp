@@ -8,6 +8,10 @@
 //                                                                      file: OK | MALFORMED | constraint <row> violated (+ the
 //                                                                      wires by name when <name>.sym exists); exit 0 = all OK,
 //                                                                      1 = some file is not, 2 = usage, I/O, another runtime
+//                  cw_witness --sha256 <name> <input(s).json>           the same run, no file: one line per instance,
+//                                                                      "<64 hex digits>  <instance index>", the SHA-256 of the
+//                                                                      .wtns the plain call writes, computed on the device
+//                                                                      (cw_get_wtns_digests); exit codes of the plain call
 // <name> is the path prefix of <name>.cwt / <name>.dat / <name>.r1cs (the .r1cs is optional: without it the
 // constraint check is skipped).  Exit code 0 = every instance produced a witness; 1 = at least one failed (the
 // reference aborts on the first failed assert, calcwit/assert_bucket.rs:75-77; here the others are still written).
@@ -113,11 +117,14 @@ int main(int argc, char **argv) {
         }
         return check_files(argv[2], argv + 3, (uint32_t)(argc - 3));
     }
+    const bool sha = argc == 4 && !strcmp(argv[1], "--sha256");
     if (argc != 4) {
-        fprintf(stderr, "Usage: %s <circuit path prefix> <input.json> <output.wtns | out_%%d.wtns>\n", argv[0]);
+        fprintf(stderr, "Usage: %s <circuit path prefix> <input.json> <output.wtns | out_%%d.wtns>\n"
+                        "       %s --sha256 <circuit path prefix> <input.json>\n", argv[0], argv[0]);
         return 2;
     }
-    const std::string name = argv[1];
+    const std::string name = sha ? argv[2] : argv[1];
+    const char *input = sha ? argv[3] : argv[2];
     const std::string r1cs = name + ".r1cs";
     FILE *probe = fopen(r1cs.c_str(), "rb");
     if (probe) fclose(probe);
@@ -133,8 +140,8 @@ int main(int argc, char **argv) {
         fclose(wl);
         if (!list.empty()) CHECK(cw_set_witness_list(c, list.data(), (uint32_t)list.size()));
     }
-    const std::vector<std::string> ins = elements(slurp(argv[2]));
-    if (ins.empty()) { fprintf(stderr, "no input objects in %s\n", argv[2]); return 2; }
+    const std::vector<std::string> ins = elements(slurp(input));
+    if (ins.empty()) { fprintf(stderr, "no input objects in %s\n", input); return 2; }
     const int device = getenv("CW_DEVICE") ? atoi(getenv("CW_DEVICE")) : 0;
     cw_batch *b = nullptr;
     CHECK(cw_batch_create(c, device, (uint32_t)ins.size(), nullptr, &b));
@@ -145,8 +152,10 @@ int main(int argc, char **argv) {
     std::vector<uint32_t> st(ins.size());
     CHECK(cw_get_status(b, st.data()));
     int failed = 0;
-    const bool many = strstr(argv[3], "%d") != nullptr;
-    if (!many && ins.size() > 1) { fprintf(stderr, "%zu inputs need an output pattern with %%d\n", ins.size()); return 2; }
+    const bool many = !sha && strstr(argv[3], "%d") != nullptr;
+    std::vector<uint8_t> digests(sha ? ins.size() * 32 : 0);
+    if (sha) CHECK(cw_get_wtns_digests(b, 0, (uint32_t)ins.size(), digests.data()));
+    if (!sha && !many && ins.size() > 1) { fprintf(stderr, "%zu inputs need an output pattern with %%d\n", ins.size()); return 2; }
     const bool logs = cw_n_log_statements(c) != 0;
     for (size_t i = 0; i < ins.size(); i++) {
         if (logs) {                 // what the reference binary prints for this input (log(...) statements), instance by instance
@@ -156,12 +165,17 @@ int main(int argc, char **argv) {
             if (cw_get_log(b, (uint32_t)i, text.data(), text.size()) < 0) { fprintf(stderr, "cw_get_log: %s\n", cw_last_error()); return 2; }
             fwrite(text.data(), 1, (size_t)n, stdout);
         }
+        if (sha) {                  // every instance has a line: the digest is produced whatever the status word says
+            for (int k = 0; k < 32; k++) printf("%02x", digests[i * 32 + k]);
+            printf("  %zu\n", i);
+        }
         if (st[i]) {
             fprintf(stderr, "instance %zu: %s%s%s\n", i, (st[i] & 1) ? "Failed assert " : "", (st[i] & 2) ? "division by zero " : "",
                     (st[i] & 4) ? "R1CS row violated" : "");
             failed++;
             continue;
         }
+        if (sha) continue;
         char path[4096];
         if (many) snprintf(path, sizeof path, argv[3], (int)i);
         else snprintf(path, sizeof path, "%s", argv[3]);

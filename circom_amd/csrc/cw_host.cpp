@@ -3913,6 +3913,62 @@ extern "C" int cw_get_r1cs_products(cw_batch *b, uint32_t parts, uint32_t row0, 
     });
 }
 
+// ---- witness digests (cw_wtns_digest.h) ----
+// SHA-256 of the bytes cw_write_wtns would write for the instances [first, first + count), 32 bytes each at d_out, one kernel per
+// table layout (cw_kernels.h), walking the engines as device_egress does:
+//   64-bit runtime     cw64_wtns_digest_kernel reads V64 through the witness list - also in the supplied-witness state
+//   bit-plane batches  cw_bits_wtns_digest_kernel on the table's masks; the digests of the instances the side batch re-ran are
+//                      written over from there, one launch per run of consecutive instances, and a side batch that holds the whole
+//                      batch serves the range alone.  The first egress after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_wtns_digest_kernel<MONT>
+// The plan (header words, lengths) is made per call from the circuit's CURRENT witness list and travels as a kernel argument.
+static int digest_egress(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
+    const cw_circuit *c = b->c;
+    const cwdig::Plan plan = cwdig::make_plan(cw_element_bytes(c), (const uint8_t *)c->q.w, c->n_witness);
+    if (c->is64) {
+        HIPCHK(cwk64_wtns_digest(b->stream, b->d_V64, b->d_w2s, b->Bp, first, count, d_out, plan));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return digest_egress(b->fb, first, count, d_out);
+        HIPCHK(cwk_bits_wtns_digest(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot, first, count, d_out, plan));
+        return cw_rerun_runs(b->fb_inst, first, count, [&](uint32_t pos, uint32_t len, uint32_t off) {
+            return digest_egress(b->fb, pos, len, (char *)d_out + (size_t)off * 32);
+        });
+    }
+    HIPCHK(cwk_wtns_digest(b->stream, b->d_V, b->d_w2s, b->Bp, first, count, d_out, plan, c->mont, c->P));
+    return CW_OK;
+}
+// what both calls check first, in the order of the other getters: null / range / alignment (CW_EINVAL), the device, the state
+static int digests_ready(cw_batch *b, const void *out, uint32_t first, uint32_t count, bool device) {
+    if (!b || !out) return fail(CW_EINVAL, "null argument");
+    const char *who = device ? "cw_get_wtns_digests_device" : "cw_get_wtns_digests";
+    const char *why = cwdig::check_range(first, count, b->batch);
+    if (!why && device) why = cwdig::check_device(out);
+    if (why) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    return list_state(b, who);
+}
+extern "C" int cw_get_wtns_digests_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out) {
+    if (int rc = digests_ready(b, d_out, first, count, true)) return rc;
+    if (count == 0) return CW_OK;
+    return digest_egress(b, first, count, d_out);
+}
+// Host image: pieces are staged in d_bulk (cw_pieces / piece_rows, as get_witnesses_host does) and copied to their place.
+// Synchronised before the staging buffer is written again and before returning.
+extern "C" int cw_get_wtns_digests(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out) {
+    if (int rc = digests_ready(b, out, first, count, false)) return rc;
+    if (count == 0) return CW_OK;
+    const uint32_t per = piece_rows(32, count);
+    HIPCHK(b->d_bulk.grow((size_t)per * 32));
+    return cw_pieces(count, per, [&](uint32_t done, uint32_t m) {
+        if (int rc = digest_egress(b, first + done, m, b->d_bulk)) return rc;
+        HIPCHK(hipMemcpyAsync(out + (size_t)done * 32, b->d_bulk, (size_t)m * 32, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return CW_OK;
+    });
+}
+
 extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]) {
     if (!b || !out) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch || slot >= b->c->n_signals) return fail(CW_EINVAL, "instance or slot out of range");
@@ -3955,16 +4011,15 @@ extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint
 
 // writeBinWitness (main.cpp:288-334): the header, then the body of n_witness elements of n8 bytes.  n8 = the prime's byte
 // length: 32 for the 4-limb primes, 8 for the 64-bit runtime (common64/main.cpp writeBinWitness).
+// The header bytes are cwdig::build_header's (cw_wtns_digest.h): the file and cw_get_wtns_digests cannot drift.
 static int write_wtns_file(const cw_circuit *c, const char *path, const uint8_t *body) {
     FILE *f = fopen(path, "wb");
     if (!f) return fail(CW_EIO, std::string("cannot open for writing: ") + path);
-    const uint32_t version = 2, nsec = 2, id1 = 1, n8 = cw_element_bytes(c), id2 = 2, nw = c->n_witness;
-    const uint64_t len1 = 8 + n8, len2 = (uint64_t)n8 * nw;
-    bool ok = fwrite("wtns", 4, 1, f) == 1;
-    ok &= fwrite(&version, 4, 1, f) == 1 && fwrite(&nsec, 4, 1, f) == 1;
-    ok &= fwrite(&id1, 4, 1, f) == 1 && fwrite(&len1, 8, 1, f) == 1;
-    ok &= fwrite(&n8, 4, 1, f) == 1 && fwrite(c->q.w, n8, 1, f) == 1 && fwrite(&nw, 4, 1, f) == 1;
-    ok &= fwrite(&id2, 4, 1, f) == 1 && fwrite(&len2, 8, 1, f) == 1;
+    const uint32_t n8 = cw_element_bytes(c);
+    const uint64_t len2 = (uint64_t)n8 * c->n_witness;
+    uint8_t hdr[cwdig::HDR_MAX];
+    const uint32_t hlen = cwdig::build_header(n8, (const uint8_t *)c->q.w, c->n_witness, hdr);
+    bool ok = fwrite(hdr, 1, hlen, f) == hlen;
     ok &= fwrite(body, 1, len2, f) == len2;
     ok &= fclose(f) == 0;
     return ok ? CW_OK : fail(CW_EIO, std::string("short write: ") + path);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "cw_tape.h"
+#include "cw_wtns_digest.h"
 
 // `mont`: the value table holds Montgomery forms x R' (lower.py pass A6): init writes R' into the constant-one slot, ingest
 // multiplies by R'^2, the gathers by 1, the R1CS check compares mmul(A~, B~) with C~
@@ -97,6 +98,16 @@ hipError_t cwk_bits_products(hipStream_t s, const void *T, uint64_t slots, uint3
                              const FpParams &P);
 hipError_t cwk64_products(hipStream_t s, const void *V, const uint32_t *rowptr, const void *terms, uint32_t parts, uint32_t row0, uint32_t n_rows,
                           uint32_t Bp, uint32_t first, uint32_t count, void *d_out);
+// witness digests (cw_get_wtns_digests*, cw_wtns_digest.h), one kernel per table layout: d_out[j] = the 32 bytes of SHA-256 over the
+// .wtns file of instance first + j (header of `plan`, then the entries of w2s / wslot as canonical little-endian elements of
+// plan.n8 bytes), j < count; d_out 16-byte aligned.  Lane = instance, one wave per table group of 64 instances that the range
+// touches; nothing else is written.
+hipError_t cwk_wtns_digest(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t Bp, uint32_t first, uint32_t count, void *d_out,
+                           const cwdig::Plan &plan, bool mont, const FpParams &P);
+hipError_t cwk_bits_wtns_digest(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t first, uint32_t count,
+                                void *d_out, const cwdig::Plan &plan);
+hipError_t cwk64_wtns_digest(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t Bp, uint32_t first, uint32_t count, void *d_out,
+                             const cwdig::Plan &plan);
 // instance lists (cw_select_instances*, cw_get_witnesses_at*, cw_select.h).
 //   cwk_select        d_idx[0 .. *d_n) = the instances i < batch with (w(i) & mask) == want, ascending; w(i) = status[i], or, with
 //                     fbidx (instance -> position in the side batch or negative) and fbidx[i] in [0, n_fb), fbstatus[fbidx[i]].

@@ -14,6 +14,7 @@
 #include "cw_select.h"
 #include "cw_columns.hip.h"
 #include "cw_list.hip.h"
+#include "cw_wtns_digest.h"
 
 #define CW_BLOCK 256
 
@@ -1629,4 +1630,49 @@ hipError_t cwk_products(hipStream_t s, const void *V, const uint32_t *rowptr, co
                            (uint4 *)d_out + (size_t)off * 2, P);
         return hipGetLastError();
     });
+}
+
+// ---- witness digests (cw_get_wtns_digests*, cw_wtns_digest.h) ----------------------------------------------------------------
+// SHA-256 of the .wtns file of every instance, n8 = 32: lane = instance, a wave owns the table group (first >> 6) + blockIdx.x and
+// walks the message with cwdig::walk - two elements per block, each the two 16-byte halves at (slot * 2 * Bp + instance) * 16 and
+// + Bp * 16 (1 KiB contiguous per wave and load, the slot a scalar load), requested a block ahead of the rounds and kept as they
+// were loaded; MONT: fe_out_of_mont runs per element when the block is put together.  Lanes outside [first, first + count) read
+// the padded table (Bp is a multiple of 256) and store nothing.
+template <bool MONT>
+struct DigestSrc {
+    static constexpr uint32_t EW = 8, H = 19, RUN = 1;
+    struct Raw { uint4 lo, hi; };
+    const uint4 *__restrict__ Vj;                         // column of the lane's instance
+    const uint32_t *__restrict__ w2s;
+    uint32_t Bp;
+    const FpParams &P;
+    __device__ __forceinline__ Raw fetch(uint32_t k) const {
+        const size_t base = (size_t)w2s[k] * 2 * Bp;
+        return Raw{Vj[base], Vj[base + Bp]};
+    }
+    __device__ __forceinline__ void words(const Raw &r, uint32_t w[8]) const {
+        uint4 lo = r.lo, hi = r.hi;
+        if (MONT) fe_out_of_mont(lo, hi, P);
+        w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w;
+        w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
+    }
+};
+template <bool MONT>
+__global__ void __launch_bounds__(64)
+cw_wtns_digest_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t Bp, uint32_t first, uint32_t count,
+                      uint4 *__restrict__ out, cwdig::Plan plan, FpParams P) {
+    const uint32_t inst = cwdig::wave_group(first, blockIdx.x) * 64u + threadIdx.x;
+    DigestSrc<MONT> src{V + inst, w2s, Bp, P};
+    uint32_t st[8];
+    cwdig::walk(plan, src, st);
+    cwdig::store_digest(out, first, count, inst, st);
+}
+// digests [count][32] of the instances [first, first + count): one wave per table group of the range; d_out 16-byte aligned
+hipError_t cwk_wtns_digest(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t Bp, uint32_t first, uint32_t count, void *d_out,
+                           const cwdig::Plan &plan, bool mont, const FpParams &P) {
+    if (count == 0) return hipSuccess;
+    if (((uintptr_t)d_out & 15) || plan.n8 != 32 || plan.n_witness == 0 || (uint64_t)first + count > Bp) return hipErrorInvalidValue;
+    const auto kernel = mont ? cw_wtns_digest_kernel<true> : cw_wtns_digest_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(cwdig::n_groups(first, count)), dim3(64), 0, s, (const uint4 *)V, w2s, Bp, first, count, (uint4 *)d_out, plan, P);
+    return hipGetLastError();
 }

@@ -33,7 +33,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "cw_wtns_digest.h", "cw_sha256.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -127,6 +127,8 @@ _SIGS = {
     "cw_get_witnesses_at_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cw_get_witnesses_at_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_get_witnesses_at_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_get_wtns_digests": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_get_wtns_digests_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_write_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtnsb": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cw_set_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -627,6 +629,21 @@ class Batch:
         """the same with the element of the .wtns files ([count][n_witness][circuit.element_bytes]): 8 bytes per value for
         circuits of the 64-bit runtime, witnesses_device for every other"""
         _chk(lib().cw_get_witnesses_device_n8(self.h, first, count, C.c_void_p(d_ptr)))
+
+    def wtns_digests(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint8 [count][32]: hashlib.sha256(the bytes write_wtns(first + j, ..) would write).digest() of every instance of the
+        range, computed on the device (cw_get_wtns_digests); no witness leaves it"""
+        count = self.n - first if count is None else count
+        out = np.zeros((max(count, 0), 32), dtype=np.uint8)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the range)
+        ptr = out.ctypes.data_as(C.c_void_p) if out.size else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _chk(lib().cw_get_wtns_digests(self.h, first, count, ptr))
+        return out
+
+    def wtns_digests_device(self, first: int, count: int, dptr: int) -> None:
+        """the same into device memory: [count][32] at dptr, 16-byte aligned; asynchronous on the batch's stream
+        (cw_get_wtns_digests_device)"""
+        _chk(lib().cw_get_wtns_digests_device(self.h, first, count, C.c_void_p(dptr)))
 
     def device_values(self):
         """(device pointer, bytes, padded batch) of the value table (cw_device_values; layout: include/circom_amd.h)"""

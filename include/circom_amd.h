@@ -491,6 +491,37 @@ int cw_get_witnesses_at_device(cw_batch *b, uint32_t entry0, uint32_t n, const v
                                void *d_out, void *d_bad);
 int cw_get_witnesses_at_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, const void *d_idx, uint32_t n_idx, const void *d_n_idx,
                                   void *d_out, void *d_bad);
+/* ---- witness digests: SHA-256 of every instance's .wtns on the device, every engine ------------------------------------------
+ * This project states correctness as the SHA-256 of a `.wtns` file (tests/golden/: wtns_sha256 of what the reference runtime
+ * wrote).  These calls compute that hash where the table lies: 32 bytes per instance leave the device instead of the witness.
+ * A caller compares a whole batch with a list of reference hashes or with another machine's batch, content-addresses or
+ * deduplicates witnesses, keeps an audit record - and no witness is moved.
+ *   digest       out[j] = the 32 digest bytes, in the order hashlib.sha256(..).digest() and sha256sum give them, of exactly the
+ *                bytes cw_write_wtns(b, first + j, path) writes at that moment: the header of writeBinWitness (main.cpp:288-334)
+ *                with n8 = cw_element_bytes, the circuit's prime and nWitness = the CURRENT cw_n_witness (a list shortened by
+ *                cw_set_witness_list counts), then the canonical little-endian elements in witness-list order.  A table of
+ *                Montgomery forms is converted on the way, as every egress does.  Digests are produced whatever the status
+ *                word says, as the file calls do.
+ *   errors       in the order of the other getters: a null batch or pointer; first + count > batch (no 32-bit wrap); device
+ *                form: d_out not 16-byte aligned (the pointer is not touched): CW_EINVAL.  Then the device (a host-only batch:
+ *                CW_EDEVICE), then the state: CW_ESTATE "... before cw_run" for a batch that has neither run nor been supplied,
+ *                "witnesses missing for N instances" for a supplied table with gaps, as cw_get_r1cs_products answers; a complete
+ *                supplied table is served.
+ *   empty        count == 0: CW_OK, nothing is written.
+ *   lifetime     the device form is asynchronous on the batch's stream - with the one exception of every device egress: the
+ *                first one after a cw_run of a bit-plane batch waits for the evaluation.  The host form stages pieces in the
+ *                batch's bulk buffer and synchronises before it returns.  The calls only read the table: status words, first-bad
+ *                rows, the timing marks, a captured cw_run_check graph and the supplied state stay as they were.
+ *   engines      lane = instance, one wave per table group of 64 instances; SHA-256 is serial per message, so a small batch of
+ *                huge witnesses is bound by the latency of one lane.  64-bit runtime (csrc/cw64.hip cw64_wtns_digest_kernel,
+ *                also in the supplied-witness state), 256-bit schedule (csrc/cw_kernels.hip cw_wtns_digest_kernel, canonical and
+ *                Montgomery-form tables), bit-plane batches (csrc/cw_bits.hip cw_bits_wtns_digest_kernel, both table layouts; the
+ *                digests of the instances the 256-bit side batch re-ran are written over from there).  One text of the header
+ *                bytes, the message walk and the compression function serves the kernels, the file writers and the CPU replay
+ *                (csrc/cw_wtns_digest.h, csrc/cw_sha256.h).
+ *   not here     an index-list form; one message split over lanes; other hash functions. */
+int cw_get_wtns_digests(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out);
+int cw_get_wtns_digests_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out);
 /* host-only: build and hazard-check the LDS staging plan of the R1CS check kernel for `chunks` row chunks
    and `entries` 2-KiB LDS entries per wave (0 = the defaults cw_batch_create would pick for `batch`).
    out[8] = {chunks, loads, terms, filler loads, distinct wires, entries, prefetch depth, 0}. */
