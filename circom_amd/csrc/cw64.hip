@@ -464,6 +464,72 @@ __global__ void __launch_bounds__(256) cw64_pack_rows_kernel(const uint64_t *__r
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * EG_S + lane];
 }
 
+// Signal columns out (cw_get_signals_range*): value k of row j = signal signal0 + k of instance first + j as a little-endian
+// unsigned integer of W bytes (1, 2, 4, 8 or 32) at out + j * stride + k * W.  Here slot = signal id, so there is no list to go
+// through.  The tile of the two kernels above: a workgroup of four waves owns 64 instances (blockIdx.y) x EG_T signals (blockIdx.x).
+//   read    lane = instance.  Wave w takes the signals w, w + 4, ... of the tile: the slot is wave-uniform, every read 512
+//           contiguous bytes, the 16 loads of a wave issued before the first value is used.  Lanes past `count` and signals past
+//           n read nothing and count as 0.
+//   report  W < 8: a value >= 2^(8 W) leaves as its low W bytes; after a ballot (under the lane's own row condition: a dead
+//           lane holds zeros) one lane reports the wave's lowest such instance, report0 + j, with atomicMin - at most one atomic
+//           per wave.  `word` may be nullptr; the caller fills it first.  W = 8 and W = 32 hold every residue.
+//   stage   tile[signal][instance] with rows of EG_S = 65 words: the row-wise write and the column-wise 8-byte read of
+//           cw64_egress_kernel, conflict-free by the bank arithmetic written out there (from the documented bank rules; no
+//           bank-conflict counter pass was taken on this kernel).
+//   write   wave w takes the instances w, w + 4, ...; consecutive lanes = consecutive values of ONE row: a store covers nk * W
+//           contiguous bytes (W < 4: byte / short stores of consecutive lanes, which the memory pipeline merges per line);
+//           W = 32: 16-byte pieces {value, 0} / {0, 0}, two stores per row of the tile, as the egress kernel writes them.
+//           Nothing is written behind value n - 1 of a row, and no row past `count`.
+// `out` and `stride` are multiples of W (of 16 for W = 32).
+template <int W>
+__global__ void __launch_bounds__(256) cw64_signals_kernel(const uint64_t *__restrict__ V, uint32_t signal0, uint32_t n, uint32_t Bp,
+                                                           uint32_t first, uint32_t count, uint32_t report0, uint8_t *__restrict__ out,
+                                                           size_t stride, uint32_t *word) {
+    __shared__ uint64_t tile[EG_T * EG_S];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
+    const uint32_t nk = n - k0 < EG_T ? n - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool ok = lane < nj;
+    const uint64_t *Vj = V + first + j0 + (ok ? lane : 0u);
+    uint64_t v[EG_T / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        const uint32_t k = wave + 4 * i;
+        const uint32_t slot = signal0 + k0 + (k < nk ? k : 0u);      // always a signal of the range
+        v[i] = k < nk && ok ? Vj[(size_t)slot * Bp] : 0;
+    }
+    bool wide = false;
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        if (W < 8) wide |= (v[i] >> (8 * (W & 7))) != 0;
+        tile[(wave + 4 * i) * EG_S + lane] = v[i];
+    }
+    if (W < 8) {
+        const uint64_t who = __builtin_amdgcn_ballot_w64(wide);
+        if (who && word && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(word, report0 + j0 + lane);
+    }
+    __syncthreads();
+    for (uint32_t j = wave; j < nj; j += 4) {
+        uint8_t *row = out + (size_t)(j0 + j) * stride + (size_t)k0 * W;
+        if (W == 32) {
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t p = lane + 64 * h, k = p >> 1;
+                if (k < nk) {
+                    const uint64_t x = p & 1u ? 0 : tile[k * EG_S + j];
+                    ((uint4 *)row)[p] = make_uint4((uint32_t)x, (uint32_t)(x >> 32), 0, 0);
+                }
+            }
+        } else if (lane < nk) {
+            const uint64_t x = tile[lane * EG_S + j];
+            if (W == 8) ((uint64_t *)row)[lane] = x;
+            if (W == 4) ((uint32_t *)row)[lane] = (uint32_t)x;
+            if (W == 2) ((uint16_t *)row)[lane] = (uint16_t)x;
+            if (W == 1) row[lane] = (uint8_t)x;
+        }
+    }
+}
+
 // R1CS products (cw_get_r1cs_products*): out[j][p][k] = the part's sum of coefficient * w[wire] over the terms of constraint
 // row0 + k in instance first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order:
 // rowptr[3 row + part] .. rowptr[3 row + part + 1] into terms {slot, 0, coefficient lo, hi}.  The shape of the kernels above: a
@@ -795,6 +861,22 @@ hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, ui
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8,
                        d_word);
     return hipGetLastError();
+}
+// signal columns out: signal tiles of EG_T in gridDim.x (n is not limited), tiles of 64 instances in gridDim.y - a launch holds at
+// most 65 535 of those, a larger count goes in several launches (cw_pieces.h), none behind one that failed.  `word` (or nullptr)
+// takes an atomicMin of report0 + j for every instance j that held a value >= 2^(8 elem_bytes); the caller fills it first.
+hipError_t cwk64_signals(hipStream_t s, const void *V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t report0, void *d_values, size_t stride, uint32_t elem_bytes, uint32_t *d_word) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const size_t a = elem_bytes == 32 ? 16 : elem_bytes;
+    const auto kernel = elem_bytes == 1 ? cw64_signals_kernel<1> : elem_bytes == 2 ? cw64_signals_kernel<2> : elem_bytes == 4 ? cw64_signals_kernel<4>
+                      : elem_bytes == 8 ? cw64_signals_kernel<8> : elem_bytes == 32 ? cw64_signals_kernel<32> : nullptr;
+    if (!kernel || ((uintptr_t)d_values % a) || (stride % a) || stride / elem_bytes < n || ((uintptr_t)d_word & 3)) return hipErrorInvalidValue;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n + EG_T - 1) / EG_T, (m + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, signal0, n, Bp, first + done,
+                           m, report0 + done, (uint8_t *)d_values + (size_t)done * stride, stride, d_word);
+        return hipGetLastError();
+    });
 }
 // R1CS products [count][n_sel][n_rows] of 8-byte residues: instance tiles in gridDim.x, row tiles of 64 in gridDim.y, a range of
 // more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one that failed

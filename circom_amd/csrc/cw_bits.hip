@@ -897,6 +897,68 @@ cw_bits_masks_to_rows_kernel(const uint64_t *__restrict__ T, uint64_t slots, uin
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * ROWS_S + lane];
 }
 
+// ---- signal columns out from the bit table (cw_get_signals_range*) --------------------------------------------------------
+// Value k of row j = signal signal0 + k of instance first + j, 0 or 1, as a little-endian unsigned integer of W bytes (1, 2, 4, 8
+// or 32) at out + (j) * stride + k * W.  A value is one bit of a mask the table already holds per group, so nothing is
+// transposed through LDS: lane = signal.  `sigslot` is the batch's signal -> slot map (cw_batch_signal_slots) on the device.
+// A workgroup of four waves owns 64 signals (blockIdx.x) x one CHUNK of 32 groups = 2 048 instances (chunk c0 + blockIdx.y, counted
+// from instance 0 whatever `first` is); wave w takes the groups 8 w .. 8 w + 7 of the chunk.
+//   read    lane k loads the eight masks of slot(signal0 + k0 + k) for the wave's groups.  sh = 5: they are 64 contiguous,
+//           64-byte aligned bytes of the slot's 256-byte row - four 16-byte loads -, and the four waves of the workgroup read the
+//           whole row between them (the padding groups of the last chunk are part of the allocation).  sh = 0: eight 8-byte
+//           loads, `slots` words apart; groups outside the range are not read.
+//   write   for each instance i of a group the wave stores (mask >> i) & 1 of its 64 signals as one contiguous run of 64 values:
+//           64 W bytes per store (W = 32: two stores of 16-byte pieces, {bit, 0, 0, 0} and zeros).  Only the instances of [first,
+//           first + count) are written, nothing behind value n - 1 of a row.
+// A bit table holds no value that is too wide: there is no word.  Instances the 256-bit side batch re-ran hold garbage here: the
+// host writes them over from there (cw_kernels.hip cw_signals_kernel with the instance -> side-batch map).
+template <int W>
+__global__ void __launch_bounds__(256)
+cw_bits_signals_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ sigslot, uint32_t signal0,
+                       uint32_t n, uint32_t first, uint32_t count, uint32_t c0, uint8_t *__restrict__ out, size_t stride) {
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k = blockIdx.x * 64u + lane;
+    const uint32_t g0 = (c0 + blockIdx.y) * 32u + wave * 8u;               // this wave's eight groups
+    const uint64_t end = (uint64_t)first + count, w_lo = (uint64_t)g0 * 64u, w_hi = w_lo + 512u;
+    const uint64_t lo = w_lo > first ? w_lo : first, hi = w_hi < end ? w_hi : end;
+    if (lo >= hi || k >= n) return;                                        // (no barrier in this kernel)
+    const uint32_t sl = sigslot[signal0 + k];
+    uint64_t m[8];
+    if (lsh == 5u) {
+        const uint4 *p = (const uint4 *)(T + cwlayout::element(slots, 5u, g0, sl));
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) {
+            const uint4 x = p[q];
+            m[2 * q] = (uint64_t)x.x | ((uint64_t)x.y << 32);
+            m[2 * q + 1] = (uint64_t)x.z | ((uint64_t)x.w << 32);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) {
+            const uint64_t base = (uint64_t)(g0 + q) * 64u;
+            m[q] = base < hi && base + 64u > lo ? T[cwlayout::element(slots, lsh, g0 + q, sl)] : 0;
+        }
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+        const uint64_t base = (uint64_t)(g0 + q) * 64u;
+        if (base >= hi || base + 64u <= lo) continue;                      // wave-uniform
+        const uint32_t i_lo = lo > base ? (uint32_t)(lo - base) : 0u, i_hi = hi - base < 64u ? (uint32_t)(hi - base) : 64u;
+        uint8_t *row = out + (size_t)(base + i_lo - first) * stride + (size_t)k * W;
+        for (uint32_t i = i_lo; i < i_hi; i++, row += stride) {
+            const uint32_t bit = (uint32_t)(m[q] >> i) & 1u;
+            if (W == 32) {
+                ((uint4 *)row)[0] = make_uint4(bit, 0u, 0u, 0u);
+                ((uint4 *)row)[1] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (W == 8) *(uint64_t *)row = bit;
+            if (W == 4) *(uint32_t *)row = bit;
+            if (W == 2) *(uint16_t *)row = (uint16_t)bit;
+            if (W == 1) *row = (uint8_t)bit;
+        }
+    }
+}
+
 // ---- R1CS products from the bit table (cw_get_r1cs_products*) -------------------------------------------------------------
 // out[j][p][k] (32 bytes, canonical) = the part's sum of coefficient * w[wire] over the terms of constraint row0 + k in instance
 // first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order: rowptr[3 row + part]
@@ -1315,6 +1377,24 @@ hipError_t cwk_bits_masks_to_rows(hipStream_t s, const void *T, uint64_t slots, 
     const auto kernel = msb ? cw_bits_masks_to_rows_kernel<true> : cw_bits_masks_to_rows_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint64_t *)T, slots, sh, wslot, n, first, count, (uint64_t *)d_rows, stride / 8);
     return hipGetLastError();
+}
+// signal columns out from the bit table: tiles of 64 signals in gridDim.x, the chunks of 2 048 instances that [first, first +
+// count) touches in gridDim.y - a launch holds at most 65 535 of those, more go in several launches (cw_pieces.h), none behind one
+// that failed.  d_values is the row of instance `first`.
+hipError_t cwk_bits_signals(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *sigslot, uint32_t signal0, uint32_t n,
+                            uint32_t first, uint32_t count, void *d_values, size_t stride, uint32_t elem_bytes) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const size_t a = elem_bytes == 32 ? 16 : elem_bytes;
+    const auto kernel = elem_bytes == 1 ? cw_bits_signals_kernel<1> : elem_bytes == 2 ? cw_bits_signals_kernel<2>
+                      : elem_bytes == 4 ? cw_bits_signals_kernel<4> : elem_bytes == 8 ? cw_bits_signals_kernel<8>
+                      : elem_bytes == 32 ? cw_bits_signals_kernel<32> : nullptr;
+    if (!kernel || ((uintptr_t)d_values % a) || (stride % a) || stride / elem_bytes < n) return hipErrorInvalidValue;
+    const uint32_t c_lo = first >> 11, c_hi = (uint32_t)(((uint64_t)first + count - 1) >> 11);
+    return cw_pieces(c_hi - c_lo + 1, 65535u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n + 63) / 64, m), dim3(256), 0, s, (const uint64_t *)T, slots, sh, sigslot, signal0, n, first, count,
+                           c_lo + done, (uint8_t *)d_values, stride);
+        return hipGetLastError();
+    });
 }
 // R1CS products [count][n_sel][n_rows] of 32-byte canonical residues from the bit table: instance tiles in gridDim.x, row tiles of
 // PRB_TILE in gridDim.y, a range of more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one

@@ -2,6 +2,7 @@
 // reference's semantics, kernel sequencing, result egress.  Mirrors the reference's C++ runtime
 // (code_producers/src/c_elements/common/{main.cpp,calcwit.cpp}); each function cites what it replaces.
 #include <hip/hip_runtime_api.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <array>
@@ -26,6 +27,7 @@
 #include "cw_columns.h"
 #include "cw_r1cs_products.h"
 #include "cw_select.h"
+#include "cw_signals.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
 
@@ -3969,6 +3971,96 @@ extern "C" int cw_get_wtns_digests(cw_batch *b, uint32_t first, uint32_t count, 
     });
 }
 
+// ---- signal columns out (cw_signals.h) ----
+// The mirror image of the input columns: the signals [signal0, signal0 + n) - signal ids, whether the witness list names them or
+// not - of the instances [first, first + count) as rows of elements of `eb` bytes at d_values + j * stride, one kernel per table
+// layout (cw_kernels.h), walking the engines as rows_egress does:
+//   64-bit runtime     cw64_signals_kernel reads V64[signal] - also in the supplied-witness state (signals_ready has made sure
+//                      that the witness list names the range: nothing else was written there)
+//   bit-plane batches  cw_bits_signals_kernel on the table's masks through the batch's signal -> slot map (d_sigslot); the rows
+//                      of the instances the side batch re-ran are written over from there in ONE launch of cw_signals_kernel with
+//                      the instance -> side-batch map (fb_map), and a side batch that holds the whole batch serves the range
+//                      alone.  The first egress after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_signals_kernel, canonical and Montgomery-form tables
+// `report0`: the batch's instance index of the launch's first row - a side batch reports in the caller's numbering.
+static int signals_egress(cw_batch *b, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, uint32_t report0, void *d_values,
+                          size_t stride, uint32_t eb, uint32_t *d_word) {
+    const cw_circuit *c = b->c;
+    if (c->is64) {
+        HIPCHK(cwk64_signals(b->stream, b->d_V64, signal0, n, b->Bp, first, count, report0, d_values, stride, eb, d_word));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        if (b->fb && b->fb_inst.size() == b->batch) return signals_egress(b->fb, signal0, n, first, count, report0, d_values, stride, eb, d_word);
+        HIPCHK(cwk_bits_signals(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_sigslot, signal0, n, first, count, d_values, stride, eb));
+        if (!b->fb || b->fb_inst.empty()) return CW_OK;
+        if (int rc = fb_map(b)) return rc;
+        HIPCHK(cwk_signals(b->stream, b->fb->d_V, signal0, n, b->fb->Bp, first, count, report0, d_values, stride, eb, d_word, b->fb->c->mont,
+                           b->fb->c->P, (uint32_t)b->fb_inst.size(), b->d_fbindex, b->batch));
+        return CW_OK;
+    }
+    HIPCHK(cwk_signals(b->stream, b->d_V, signal0, n, b->Bp, first, count, report0, d_values, stride, eb, d_word, c->mont, c->P, 0, nullptr, 0));
+    return CW_OK;
+}
+// what both calls check first, in the order of the other getters: null / width / ranges / stride / alignment (CW_EINVAL), the
+// device, the state - and on a complete supplied table the answer of cw_get_signal for a signal the witness list does not name
+static int signals_ready(cw_batch *b, const void *values, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, size_t stride,
+                         uint32_t eb, const void *d_word, bool device) {
+    if (!b || !values) return fail(CW_EINVAL, "null argument");
+    const char *who = device ? "cw_get_signals_range_device" : "cw_get_signals_range";
+    // (cw_n_signals: the hidden log values behind the circuit's signals are not addressable)
+    if (const char *why = cwsig::check(signal0, n, b->c->n_signals - b->c->n_logv, first, count, b->batch, values, stride, eb, d_word, device))
+        return fail(CW_EINVAL, std::string(who) + ": " + why);
+    if (int rc = list_state(b, who)) return rc;
+    if (b->supplied && n) {
+        const std::vector<uint32_t> &w = b->c->w2s;                          // strictly increasing: a run of ids is a run of entries
+        const size_t at = std::lower_bound(w.begin(), w.end(), signal0) - w.begin();
+        if (at + n > w.size() || w[at] != signal0 || w[at + n - 1] != signal0 + n - 1)
+            return fail(CW_ESTATE, std::string(who) + ": no witness program has run on this table (the witnesses were supplied): a signal the "
+                                                      "witness list does not name was never written");
+    }
+    return CW_OK;
+}
+extern "C" int cw_get_signals_range_device(cw_batch *b, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, void *d_values,
+                                           size_t stride, uint32_t elem_bytes, void *d_too_wide) {
+    if (int rc = signals_ready(b, d_values, signal0, n, first, count, stride, elem_bytes, d_too_wide, true)) return rc;
+    if (d_too_wide) HIPCHK(cwk_fill32(b->stream, (uint32_t *)d_too_wide, cwsig::NONE, 1));
+    if (n == 0 || count == 0) return CW_OK;
+    return signals_egress(b, signal0, n, first, count, first, d_values, stride, elem_bytes, (uint32_t *)d_too_wide);
+}
+// Host rows of any stride and alignment: dense rows are staged in d_bulk piece by piece (cw_pieces / piece_rows, as
+// get_witnesses_host does; the word lives behind the piece, on an 8-byte boundary) and copied to their place - straight into the
+// caller's image where its rows are dense, else through a host image, n * elem_bytes bytes per row (cwsig::scatter).
+// Synchronised before the staging buffer is written again and before returning.
+extern "C" int cw_get_signals_range(cw_batch *b, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, void *values, size_t stride,
+                                    uint32_t elem_bytes, uint32_t *too_wide) {
+    if (int rc = signals_ready(b, values, signal0, n, first, count, stride, elem_bytes, nullptr, false)) return rc;
+    if (too_wide) *too_wide = cwsig::NONE;
+    if (n == 0 || count == 0) return CW_OK;
+    const size_t row = cwsig::row_bytes(n, elem_bytes);
+    const uint32_t per = piece_rows(row, count);
+    const size_t word_at = ((size_t)per * row + 7) & ~(size_t)7;
+    HIPCHK(b->d_bulk.grow(word_at + 8));
+    uint32_t *d_word = (uint32_t *)((char *)b->d_bulk.get() + word_at);
+    HIPCHK(cwk_fill32(b->stream, d_word, cwsig::NONE, 1));
+    std::vector<uint8_t> img(stride == row ? 0 : (size_t)per * row);
+    const int rc = cw_pieces(count, per, [&](uint32_t done, uint32_t m) {
+        if (int rc2 = signals_egress(b, signal0, n, first + done, m, first + done, b->d_bulk, row, elem_bytes, d_word)) return rc2;
+        uint8_t *to = (uint8_t *)values + (size_t)done * stride;
+        HIPCHK(hipMemcpyAsync(stride == row ? to : img.data(), b->d_bulk, (size_t)m * row, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (stride != row) cwsig::scatter(img.data(), n, elem_bytes, m, to, stride);
+        return CW_OK;
+    });
+    if (rc) return rc;
+    if (too_wide) {
+        HIPCHK(hipMemcpyAsync(too_wide, d_word, 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return CW_OK;
+}
+
 extern "C" int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]) {
     if (!b || !out) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch || slot >= b->c->n_signals) return fail(CW_EINVAL, "instance or slot out of range");
@@ -4266,6 +4358,24 @@ static std::string u256_dec(const uint8_t le[32]) {
     }
     return out;
 }
+// The signals a .sym file names: the lowest id and the count of the lines whose name is `name`, an element name[..] or a member
+// name.x of it - the range cw_get_signals_range* takes.  Host-only; the walk over the file is the one cw_explain makes.
+extern "C" int cw_sym_find(const char *sym_path, const char *name, uint32_t *signal0, uint32_t *n) {
+    if (!sym_path || !name || !signal0 || !n) return fail(CW_EINVAL, "null argument");
+    std::vector<uint8_t> buf;
+    struct stat st;
+    if (stat(sym_path, &st) != 0 || !S_ISREG(st.st_mode) || !read_file(sym_path, buf))    // (a directory opens, and has no length)
+        return fail(CW_EIO, std::string(".sym file not found: ") + sym_path);
+    uint32_t lo = 0, cnt = 0;
+    uint64_t gap = 0;
+    if (!*name || !cwsig::sym_find(buf, name, &lo, &cnt, &gap)) return fail(CW_EINPUT, std::string("Signal not found: ") + name);
+    if (gap)
+        return fail(CW_EINVAL, std::string("cw_sym_find: the signals of ") + name + " are not one consecutive run: " + std::to_string(lo) +
+                                   " .. " + std::to_string(gap - 1) + " match, " + std::to_string(gap) + " does not (one call per run of ids)");
+    *signal0 = lo;
+    *n = cnt;
+    return CW_OK;
+}
 extern "C" int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, char *out, size_t out_len) {
     if (!b || !out || out_len == 0) return fail(CW_EINVAL, "null argument");
     if (instance >= b->batch) return fail(CW_EINVAL, "instance out of range");
@@ -4279,17 +4389,9 @@ extern "C" int cw_explain(cw_batch *b, uint32_t instance, const char *sym_path, 
         std::vector<uint8_t> buf;
         if (!read_file(sym_path, buf)) return fail(CW_EIO, std::string(".sym file not found: ") + sym_path);
         names.assign(c->n_signals, std::string());
-        size_t i = 0;
-        while (i < buf.size()) {
-            size_t e = i;
-            while (e < buf.size() && buf[e] != '\n') e++;
-            std::string line((const char *)buf.data() + i, e - i);
-            i = e + 1;
-            size_t c1 = line.find(','), c2 = line.find(',', c1 + 1), c3 = line.find(',', c2 + 1);
-            if (c1 == std::string::npos || c2 == std::string::npos || c3 == std::string::npos) continue;
-            unsigned long sid = strtoul(line.c_str(), nullptr, 10);
-            if (sid < names.size()) names[sid] = line.substr(c3 + 1);
-        }
+        cwsig::sym_walk(buf, [&](unsigned long sid, const std::string &name) {
+            if (sid < names.size()) names[sid] = name;
+        });
     }
     auto name_of = [&](uint32_t sgn) {
         if (sgn == 0) return std::string("one");

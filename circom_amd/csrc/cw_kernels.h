@@ -85,6 +85,21 @@ hipError_t cwk64_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, ui
                            uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word);
 hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
                          uint32_t report0, bool msb, void *d_rows, size_t stride, uint32_t *d_word, bool mont, const FpParams &P);
+// signal columns OUT (cw_get_signals_range*, cw_signals.h), one kernel per table layout: value k of row j = signal signal0 + k
+// (signal ids, not witness-list positions) of instance first + j, the canonical residue as a little-endian unsigned integer of
+// elem_bytes (1, 2, 4, 8 or 32) at d_values + j * stride + k * elem_bytes, j < count; only those n * elem_bytes bytes of a row
+// are written.  d_values and stride are multiples of elem_bytes (of 16 for 32).  The two value tables report a value >= 2^(8
+// elem_bytes) - stored as its low bytes - by atomicMin(d_word, report0 + j); d_word may be nullptr, the caller fills it
+// (cwk_fill32) first.  A bit table (sigslot: the batch's signal -> slot map on the device) holds 0 / 1 only.  cwk_signals with
+// `remap` (n_remap entries) reads row j from column remap[first + j] of its table where that is in [0, batch) and leaves every
+// other row alone: the rows of a side batch written over those of the bit table, as cwk_gather_at does it for a list.
+hipError_t cwk_bits_signals(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *sigslot, uint32_t signal0, uint32_t n,
+                            uint32_t first, uint32_t count, void *d_values, size_t stride, uint32_t elem_bytes);
+hipError_t cwk64_signals(hipStream_t s, const void *V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t report0, void *d_values, size_t stride, uint32_t elem_bytes, uint32_t *d_word);
+hipError_t cwk_signals(hipStream_t s, const void *V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count, uint32_t report0,
+                       void *d_values, size_t stride, uint32_t elem_bytes, uint32_t *d_word, bool mont, const FpParams &P, uint32_t batch,
+                       const int32_t *remap, uint32_t n_remap);
 // R1CS products OUT (cw_get_r1cs_products*, cw_r1cs_products.h), one kernel per table layout: d_out[j][p][k] = the p-th part of
 // `parts` (bits 0 / 1 / 2 = A / B / C, in that order) of constraint row0 + k of the .r1cs file in instance first + j, canonical
 // residues of 32 bytes (d_out 16-byte aligned) or, 64-bit runtime, 8 bytes (8-byte aligned); dense, count x popcount(parts) x

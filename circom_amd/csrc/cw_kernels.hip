@@ -1144,6 +1144,117 @@ cw_pack_rows_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2
         for (uint32_t j = wave; j < nj; j += 4) o[(size_t)j * stride_w + lane] = tile[j * 65 + lane];
 }
 
+// ---- signal columns out (cw_get_signals_range*) -------------------------------------------------------------
+// Value k of row j = signal signal0 + k of instance first + j as a little-endian unsigned integer of W bytes (1, 2, 4, 8 or 32) at
+// out + j * stride + k * W, the canonical residue (MONT: fe_out_of_mont on the way).  The 8 x u32 table is addressed as
+// cw_gather_many_kernel addresses it; here slot = signal id, so there is no list to go through.  A workgroup of four waves owns 64
+// instances (blockIdx.y) x SG_TILE(W) signals (blockIdx.x): 16 for W = 32 - the tile and the stores of cw_gather_many_kernel -,
+// 64 for the narrow widths, whose tile holds one 8-byte word per value - the tile of cw64_signals_kernel (cw64.hip).
+//   read    lane = instance, wave w takes the signals w, w + 4, ...: the two 16-byte halves of 64 consecutive instances, 1 KiB
+//           contiguous each, the slot wave-uniform.
+//   report  W < 32: a residue with any bit from 8 W upwards set leaves as its low W bytes; after a ballot one lane reports the
+//           wave's lowest such instance, report0 + j, with atomicMin - at most one atomic per wave.  `word` may be nullptr; the
+//           caller fills it first.
+//   remap   as in cw_gather_many_kernel: with `remap` (n_remap entries) lane j reads column remap[first + j] of THIS table, and a
+//           row whose entry is negative (or not below `batch`) is LEFT ALONE - the instances a bit-plane batch re-ran are written
+//           over from the side batch's table in one launch, behind cw_bits_signals_kernel.  Without it `batch` is not used.
+//   keep    keep[64] in LDS, one dword per row of the tile (written by wave 0, read as a broadcast in the store loop).
+//   stage   W = 32: tile[signal][half][instance] of 16-byte words with rows of 65, as cw_gather_many_kernel.  W <= 8:
+//           tile[signal][instance] of 8-byte words with rows of 65, written row-wise and read column-wise: conflict-free by the
+//           arithmetic at cw64_egress_kernel (from the documented bank rules; no bank-conflict counter pass was taken here).
+//   write   consecutive lanes = consecutive values of one row.  W <= 8: wave w takes the rows w, w + 4, ...; a store covers
+//           nk * W contiguous bytes (byte / short stores of consecutive lanes for W < 4).  W = 32: 32 consecutive 16-byte pieces
+//           of a row, two rows per store instruction.  Nothing is written behind value n - 1 of a row or past `count` rows.
+// `out` and `stride` are multiples of W (of 16 for W = 32).
+template <int W, bool MONT>
+__global__ void __launch_bounds__(256)
+cw_signals_kernel(const uint4 *__restrict__ V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count, uint32_t report0,
+                  uint8_t *__restrict__ out, size_t stride, FpParams P, uint32_t batch, const int32_t *__restrict__ remap, uint32_t n_remap,
+                  uint32_t *word) {
+    constexpr uint32_t T = W == 32 ? 16u : 64u;
+    __shared__ uint4 tile[W == 32 ? T * 2 * 65 : T * 65 / 2 + 1];    // (the narrow tile is T * 65 words of 8 bytes)
+    __shared__ uint32_t keep[64];
+    const uint32_t k0 = blockIdx.x * T, i0 = blockIdx.y * 64u;
+    const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t nk = n - k0 < T ? n - k0 : T;
+    uint32_t col = first + i0 + lane;
+    bool ok = i0 + lane < count;
+    if (remap) {
+        const int32_t r = ok && col < n_remap ? remap[col] : -1;
+        ok = r >= 0 && (uint32_t)r < batch;
+        col = (uint32_t)r;
+    }
+    // every wave maps lane -> row alike, so this is one decision for the workgroup, ahead of its barrier: a tile in which no
+    // row is remapped costs the overlay one load per lane
+    if (remap && __builtin_amdgcn_ballot_w64(ok) == 0) return;
+    if (wv == 0) keep[lane] = ok;
+    const uint4 *Vj = V + (ok ? col : 0u);
+    uint64_t *tile8 = (uint64_t *)tile;
+    bool wide = false;
+    if (W == 32) {
+        for (uint32_t e = wv; e < nk; e += 4) {
+            uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+            if (ok) {
+                const size_t base = (size_t)(signal0 + k0 + e) * 2 * Bp;
+                lo = Vj[base];
+                hi = Vj[base + Bp];
+                if (MONT) fe_out_of_mont(lo, hi, P);
+            }
+            tile[(e * 2 + 0) * 65 + lane] = lo;
+            tile[(e * 2 + 1) * 65 + lane] = hi;
+        }
+    } else {
+        // four signals at a time: their eight loads stand ahead of the first conversion (a signal past nk takes the tile's first
+        // slot - always one of the range - and is dropped)
+        for (uint32_t e0 = wv; e0 < nk; e0 += 16) {
+            uint4 lo[4], hi[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) {
+                const uint32_t e = e0 + 4 * u;
+                const size_t base = (size_t)(signal0 + k0 + (e < nk ? e : 0u)) * 2 * Bp;
+                lo[u] = ok ? Vj[base] : make_uint4(0, 0, 0, 0);
+                hi[u] = ok ? Vj[base + Bp] : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) {
+                const uint32_t e = e0 + 4 * u;
+                if (e >= nk) break;                                  // wave-uniform
+                if (MONT && ok) fe_out_of_mont(lo[u], hi[u], P);
+                const uint32_t above = (W == 1 ? lo[u].x >> 8 : W == 2 ? lo[u].x >> 16 : 0u) | (W <= 4 ? lo[u].y : 0u) | lo[u].z | lo[u].w |
+                                       hi[u].x | hi[u].y | hi[u].z | hi[u].w;
+                wide |= above != 0;
+                tile8[e * 65 + lane] = (uint64_t)lo[u].x | ((uint64_t)lo[u].y << 32);
+            }
+        }
+    }
+    if (W < 32) {
+        const uint64_t who = __builtin_amdgcn_ballot_w64(wide);
+        if (who && word && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(word, report0 + i0 + lane);
+    }
+    __syncthreads();
+    if (W == 32) {
+        constexpr uint32_t PIECES = 32, PER = 2;
+        const uint32_t piece = lane % PIECES, sub = lane / PIECES, e = piece >> 1, h = piece & 1;
+        for (uint32_t ii = wv * PER + sub; ii < 64; ii += 4 * PER)
+            if (e < nk && keep[ii]) {
+                const uint4 v = tile[(e * 2 + h) * 65 + ii];
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                u32x4 w = {v.x, v.y, v.z, v.w};
+                __builtin_nontemporal_store(w, (u32x4 *)(out + (size_t)(i0 + ii) * stride + (size_t)k0 * 32) + piece);
+            }
+    } else {
+        for (uint32_t j = wv; j < 64; j += 4)
+            if (keep[j] && lane < nk) {
+                uint8_t *row = out + (size_t)(i0 + j) * stride + (size_t)k0 * W;
+                const uint64_t x = tile8[lane * 65 + j];
+                if (W == 8) ((uint64_t *)row)[lane] = x;
+                if (W == 4) ((uint32_t *)row)[lane] = (uint32_t)x;
+                if (W == 2) ((uint16_t *)row)[lane] = (uint16_t)x;
+                if (W == 1) row[lane] = (uint8_t)x;
+            }
+    }
+}
+
 // ---- R1CS products (cw_get_r1cs_products*) ------------------------------------------------------------------
 // out[j][p][k] (32 bytes, canonical) = the part's sum of coefficient * w[wire] over the terms of constraint row0 + k in instance
 // first + j, for the parts of `parts` in the order A, B, C.  The plan (cw_r1cs_products.h) is in FILE order: rowptr[3 row + part]
@@ -1612,6 +1723,41 @@ hipError_t cwk_pack_rows(hipStream_t s, const void *V, const uint32_t *w2s, uint
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, (const uint4 *)V, w2s, n, Bp, first, count, report0, (uint64_t *)d_rows, stride / 8, d_word,
                        one_lo, one_hi);
     return hipGetLastError();
+}
+// signal columns out from the 8 x u32 table: signal tiles (16 for 32-byte elements, else 64) in gridDim.x, tiles of 64 instances in
+// gridDim.y - a launch holds at most 65 535 of those, a larger count goes in several launches (cw_pieces.h), none behind one
+// that failed.  `word` (or nullptr) takes an atomicMin of report0 + j for every row j written that held a value >= 2^(8
+// elem_bytes); the caller fills it first.  With `remap` (n_remap entries) row j is read from column remap[first + j] where that
+// is in [0, batch) and left alone otherwise.
+template <int W>
+static hipError_t signals_launch(hipStream_t s, const void *V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count,
+                                 uint32_t report0, void *d_values, size_t stride, uint32_t *d_word, bool mont, const FpParams &P, uint32_t batch,
+                                 const int32_t *remap, uint32_t n_remap) {
+    constexpr uint32_t T = W == 32 ? 16u : 64u;
+    const auto kernel = mont ? cw_signals_kernel<W, true> : cw_signals_kernel<W, false>;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n + T - 1) / T, (m + 63) / 64), dim3(256), 0, s, (const uint4 *)V, signal0, n, Bp, first + done, m,
+                           report0 + done, (uint8_t *)d_values + (size_t)done * stride, stride, P, batch, remap, n_remap, d_word);
+        return hipGetLastError();
+    });
+}
+hipError_t cwk_signals(hipStream_t s, const void *V, uint32_t signal0, uint32_t n, uint32_t Bp, uint32_t first, uint32_t count, uint32_t report0,
+                       void *d_values, size_t stride, uint32_t elem_bytes, uint32_t *d_word, bool mont, const FpParams &P, uint32_t batch,
+                       const int32_t *remap, uint32_t n_remap) {
+    if (n == 0 || count == 0) return hipSuccess;
+    const size_t a = elem_bytes == 32 ? 16 : elem_bytes;
+    if (!a || ((uintptr_t)d_values % a) || (stride % a) || stride / elem_bytes < n || (((uintptr_t)d_word | (uintptr_t)remap) & 3))
+        return hipErrorInvalidValue;
+#define CW_SIGNALS(W) signals_launch<W>(s, V, signal0, n, Bp, first, count, report0, d_values, stride, d_word, mont, P, batch, remap, n_remap)
+    switch (elem_bytes) {
+    case 1: return CW_SIGNALS(1);
+    case 2: return CW_SIGNALS(2);
+    case 4: return CW_SIGNALS(4);
+    case 8: return CW_SIGNALS(8);
+    case 32: return CW_SIGNALS(32);
+    }
+#undef CW_SIGNALS
+    return hipErrorInvalidValue;
 }
 // R1CS products [count][n_sel][n_rows] of 32-byte canonical residues from the 8 x u32 table: instance tiles in gridDim.x, row tiles
 // of PR_TILE in gridDim.y, a range of more than 65 535 tiles in several launches (cw_r1cs_products.h row_pieces), none behind one

@@ -33,7 +33,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_fn64.h", "cw_wtns_read.h", "cw_wtns_digest.h", "cw_sha256.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_signals.h", "cw_fn64.h", "cw_wtns_read.h", "cw_wtns_digest.h", "cw_sha256.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -116,6 +116,9 @@ _SIGS = {
     "cw_get_public_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cw_get_witness_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32)]),
     "cw_get_witness_rows_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "cw_get_signals_range": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "cw_get_signals_range_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "cw_sym_find": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cw_get_signal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p]),
     "cw_get_r1cs_first_bad": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -608,6 +611,28 @@ class Batch:
         _chk(lib().cw_get_witness_rows_device(self.h, entry0, n, first, count, C.c_void_p(d_ptr), stride, ROWS_MSB_FIRST if msb_first else 0,
                                               C.c_void_p(d_not_boolean) if d_not_boolean else None))
 
+    def signals_range(self, signal0: int, n: int, first: int = 0, count: int | None = None, elem_bytes: int = 32):
+        """signal columns out, every engine (cw_get_signals_range): ([count][n] array of uint8 / uint16 / uint32 / uint64, or
+        [count][n][32] uint8 for elem_bytes = 32; word).  Row j = instance first + j, value k = signal signal0 + k (a signal id,
+        whether the witness list names it or not), the canonical residue narrowed to elem_bytes little-endian bytes.  word:
+        0xFFFFFFFF, or the lowest instance of the range that held a value >= 2 ** (8 * elem_bytes) (its low bytes are stored)."""
+        count = self.n - first if count is None else count
+        dt = {1: np.uint8, 2: np.dtype("<u2"), 4: np.dtype("<u4"), 8: np.dtype("<u8")}.get(elem_bytes, np.uint8)
+        out = np.zeros((count, n, 32) if elem_bytes == 32 else (count, n), dtype=dt)
+        word = C.c_uint32(0)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the range)
+        ptr = out.ctypes.data_as(C.c_void_p) if out.size else C.cast(C.byref(word), C.c_void_p)
+        _chk(lib().cw_get_signals_range(self.h, signal0, n, first, count, ptr, n * elem_bytes, elem_bytes, C.byref(word)))
+        return out, word.value
+
+    def signals_range_device(self, signal0: int, n: int, first: int, count: int, d_ptr: int, stride: int, elem_bytes: int = 32,
+                             d_too_wide: int = 0) -> None:
+        """the same into device memory: row j at d_ptr + j * stride, d_ptr and stride multiples of elem_bytes (of 16 for 32), only
+        the n * elem_bytes bytes of a row are written; d_too_wide: 0 or the 4-byte aligned device address of the word;
+        asynchronous on the batch's stream (cw_get_signals_range_device)"""
+        _chk(lib().cw_get_signals_range_device(self.h, signal0, n, first, count, C.c_void_p(d_ptr), stride, elem_bytes,
+                                               C.c_void_p(d_too_wide) if d_too_wide else None))
+
     def public_rows(self, msb_first: bool = True):
         """entries 1 .. n_public of every instance as packed rows: (uint8 [batch][ceil(n_public / 8)], word).  msb_first=False is
         exactly the layout sharding.pack_bit_rows makes of the 32-byte image; for a Sha256(n) circuit the first 32 bytes of a row
@@ -690,6 +715,14 @@ class Batch:
         if n < 0:
             _chk(int(n))
         return buf.value.decode()
+
+
+def sym_find(sym_path, name: str):
+    """(signal0, n): the run of signal ids a .sym file lists under `name` - the name itself, its elements name[..] and its
+    members name.x - as cw_get_signals_range takes it (cw_sym_find; host-only, no batch needed)"""
+    s0, n = C.c_uint32(0), C.c_uint32(0)
+    _chk(lib().cw_sym_find(os.fspath(sym_path).encode(), name.encode(), C.byref(s0), C.byref(n)))
+    return s0.value, n.value
 
 
 def fp_mul_bench(q: int, a: np.ndarray, b: np.ndarray, iters: int, device: int = 0):

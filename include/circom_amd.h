@@ -332,6 +332,60 @@ int cw_get_witness_rows(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first
                         uint32_t flags, uint32_t *not_boolean);
 int cw_get_witness_rows_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, void *d_rows, size_t stride,
                                uint32_t flags, void *d_not_boolean);
+/* Signal COLUMNS out, every engine: the mirror image of cw_set_inputs_range* / cw_set_input_column*.  Every bulk egress above is
+ * addressed through the witness list and hands out the circuit's element; these two take a range of SIGNAL IDS - whether the
+ * witness list names them or not: at --O1 most signals are not in it - and the caller's record layout: a stride and a narrow
+ * little-endian element.  The verdict bit of a verifier, the bytes of a digest, a 64-bit index leave at their own width, for the
+ * whole batch, in one call.
+ *   layout       the n values of instance first + j are little-endian unsigned integers of elem_bytes in {1, 2, 4, 8, 32} and
+ *                start at values + j * stride; value k is signal signal0 + k.  The ids are those of cw_get_signal,
+ *                cw_signal_slots, the first column of the .sym file (cw_sym_find) and the wire numbers of the .r1cs of an
+ *                unsimplified system, up to cw_n_signals - 1; the hidden log values and temporaries behind them are not
+ *                addressable.  stride >= n * elem_bytes: there is no broadcast form on the way out.  Exactly n * elem_bytes
+ *                bytes of a row are written and every other byte of the image stays as it was, so a caller fills the fields of
+ *                an array of records with one call per field.  Offsets are 64-bit throughout.
+ *   values       the canonical residue < q.  A table of Montgomery forms is converted on the way out, as every egress does; the
+ *                8-byte residue of the 64-bit runtime is zero-extended for elem_bytes == 32.  A bit-plane batch delivers 0 / 1,
+ *                and for the instances its 256-bit side batch re-ran what that batch holds, which may be any residue.
+ *   too wide     a value >= 2^(8 elem_bytes) is stored as its low elem_bytes bytes and reported through one word: 0xFFFFFFFF when
+ *                every value read fitted, else the lowest instance index OF THE BATCH, within the range, that held such a value -
+ *                the contract and the mechanism of not_boolean in cw_get_witness_rows*: the call writes the word itself, in
+ *                stream order, a fill kernel, then atomicMin.  too_wide / d_too_wide may be NULL; the device word must be 4-byte
+ *                aligned.  elem_bytes == 32 never reports, and neither does elem_bytes == 8 on the 64-bit runtime.
+ *   host form    any alignment.  The image is staged in pieces through the batch's bulk buffer and copied row by row into
+ *                place, only the n * elem_bytes bytes of a row; synchronises before it returns.
+ *   device form  d_values and stride multiples of elem_bytes (of 16 for 32-byte elements), CW_EINVAL otherwise (the pointer is
+ *                not touched).  Asynchronous on the batch's stream - with the one exception of every device egress: the first
+ *                one after a cw_run of a bit-plane batch waits for the evaluation.
+ *   empty        n == 0 or count == 0: CW_OK, no byte of the image is written, the word (if given) becomes 0xFFFFFFFF.
+ *   errors       in the order of the other getters: a null batch or image; elem_bytes outside the five widths; signal0 + n >
+ *                cw_n_signals or first + count > batch (no 32-bit wrap); a stride shorter than the row; the alignments of the
+ *                device form: CW_EINVAL.  Then the device (a host-only batch: CW_EDEVICE), then the state: CW_ESTATE "... before
+ *                cw_run" for a batch that has neither run nor been supplied, "witnesses missing for N instances" for a supplied
+ *                table with gaps, and on a complete supplied table the answer of cw_get_signal when the range names a signal
+ *                the witness list does not hold (no witness program has run there).
+ *   lifetime     the calls only read the table: status words, first-bad rows, timing marks, a captured cw_run_check graph and the
+ *                supplied state stay as they were; before or after cw_check_r1cs.
+ *   memory       a bit-plane batch reads its signal -> slot map on the device (cw_batch_signal_slots, 4 bytes per signal) and,
+ *                where it has re-run instances, the instance -> side-batch map that cw_get_witnesses_at* makes (4 bytes per
+ *                instance, uploaded on first use after a resolve, freed with the batch).  The host form grows the bulk buffer.
+ *   engines      64-bit runtime (csrc/cw64.hip cw64_signals_kernel, also in the supplied-witness state), 256-bit schedule
+ *                (csrc/cw_kernels.hip cw_signals_kernel, canonical and Montgomery-form tables): lane = instance on the read,
+ *                the tile turned through LDS, consecutive lanes = consecutive values of one row on the write.  Bit-plane batches
+ *                (csrc/cw_bits.hip cw_bits_signals_kernel, both table layouts): lane = signal, a value is one bit of a mask, no
+ *                LDS; the rows of the instances the side batch re-ran are written over from there in one launch.
+ *   not here     a scattered list of signal ids (one call per run of ids, as on the input side); instance lists; big-endian
+ *                elements.
+ * cw_sym_find is host-only and needs no batch: the lowest signal id and the count of the lines of a .sym file
+ * ("id,witness,component,name" per line, as cw_explain reads it) whose name is `name` itself or begins with `name[` or `name.` -
+ * "main.out" names all 256 bits of a Sha256 output, "main.h.out[3]" one signal.  CW_EIO when the file cannot be read, CW_EINPUT
+ * "Signal not found: <name>" when nothing matches, CW_EINVAL when the matching ids are not one consecutive run (the message names
+ * the first gap). */
+int cw_get_signals_range(cw_batch *b, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, void *values, size_t stride,
+                         uint32_t elem_bytes, uint32_t *too_wide);
+int cw_get_signals_range_device(cw_batch *b, uint32_t signal0, uint32_t n, uint32_t first, uint32_t count, void *d_values, size_t stride,
+                                uint32_t elem_bytes, void *d_too_wide);
+int cw_sym_find(const char *sym_path, const char *name, uint32_t *signal0, uint32_t *n);
 /* one signal of one instance (signalValues[slot]) */
 int cw_get_signal(cw_batch *b, uint32_t instance, uint32_t slot, uint8_t out[32]);
 /* writeBinWitness (main.cpp:288-334).  Every write is checked, here and in the two calls below: a file that could not be
