@@ -17,6 +17,7 @@
 #include "cw_r1cs_products.h"
 #include "cw_columns.hip.h"
 #include "cw_list.hip.h"
+#include "cw_compare.hip.h"
 #include "cw_wtns_digest.h"
 
 #define GL_P 0xFFFFFFFF00000001ull
@@ -408,6 +409,91 @@ __global__ void __launch_bounds__(256) cw64_egress_kernel(const uint64_t *__rest
             }
         }
     }
+}
+
+// Witness compare (cw_compare_witnesses*): the range egress above with its stores turned into loads and compares.  image[j][k]
+// (EB bytes, [count][n_wit]) against entry k of the range (w2s points at its first entry, entry0 in the witness list) of instance
+// first + j: diff[j] = min(diff[j], lowest differing entry0 + k), summary as cw_compare.hip.h states it; the caller fills
+// diff[0 .. count) and summary first.  The tile, its rows of EG_S words, the read and the stage of cw64_egress_kernel<EB, false>;
+// then wave w takes the instances j = w, w + 4, ... and consecutive lanes LOAD consecutive pieces of image[j][k0 .. k0 + EG_T),
+// streaming: the 64 values, 512 contiguous bytes (8-byte form), or 16-byte pieces, 1 KiB contiguous per load, two loads per row
+// of the tile (32-byte form: an even piece must be {value, 0}, an odd piece zero - the upper 24 bytes count).  Every byte of the
+// image is requested by exactly one workgroup; lanes past `count` and entries past n_wit neither read nor write.
+//   reduce  the lanes of a load cover ascending entries of ONE instance: after a ballot the lowest differing lane notes its entry
+//           in low[] (one LDS atomic per instance and load, none for equal pieces).
+template <int EB>
+__global__ void __launch_bounds__(256) cw64_compare_kernel(const uint64_t *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit,
+                                                           uint32_t Bp, uint32_t first, uint32_t count, const uint8_t *__restrict__ image,
+                                                           uint32_t entry0, uint32_t report0, uint32_t *__restrict__ diff,
+                                                           uint32_t *__restrict__ summary) {
+    __shared__ uint64_t tile[EG_T * EG_S];
+    __shared__ uint32_t low[64];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t k0 = blockIdx.x * EG_T, j0 = blockIdx.y * 64u;
+    const uint32_t nk = n_wit - k0 < EG_T ? n_wit - k0 : EG_T, nj = count - j0 < 64u ? count - j0 : 64u;
+    const bool ok = lane < nj;
+    const uint64_t *Vj = V + first + j0 + lane;
+    if (wave == 0) low[lane] = CMP_EQUAL;
+    uint64_t v[EG_T / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) {
+        const uint32_t k = wave + 4 * i;
+        const uint32_t slot = w2s[k < nk ? k0 + k : k0];             // always an entry of the list: the scalar load needs no branch
+        v[i] = k < nk && ok ? Vj[(size_t)slot * Bp] : 0;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < EG_T / 4; i++) tile[(wave + 4 * i) * EG_S + lane] = v[i];
+    __syncthreads();
+    // CH rows of the tile at a time: eight loads of a lane are in flight before the first compare
+    constexpr uint32_t CH = EB == 8 ? 8 : 4;
+    for (uint32_t jb = wave; jb < nj; jb += 4 * CH) {                // (jb, nj and the trip count are wave-uniform)
+        if (EB == 8) {
+            uint64_t got[CH];
+#pragma unroll
+            for (uint32_t u = 0; u < CH; u++) {
+                const uint32_t j = jb + 4 * u;
+                got[u] = 0;
+                if (j < nj && lane < nk) got[u] = cmp_load8((const uint64_t *)image + (size_t)(j0 + j) * n_wit + k0 + lane);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < CH; u++) {
+                const uint32_t j = jb + 4 * u;
+                if (j < nj) {
+                    const uint64_t who = __ballot(lane < nk && got[u] != tile[lane * EG_S + j]);
+                    if (who && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(&low[j], entry0 + k0 + lane);
+                }
+            }
+        } else {
+            uint4 got[CH][2];
+#pragma unroll
+            for (uint32_t u = 0; u < CH; u++)
+#pragma unroll
+                for (uint32_t h = 0; h < 2; h++) {
+                    const uint32_t j = jb + 4 * u, p = lane + 64 * h;
+                    got[u][h] = make_uint4(0, 0, 0, 0);
+                    if (j < nj && (p >> 1) < nk) got[u][h] = cmp_load16((const uint4 *)image + ((size_t)(j0 + j) * n_wit + k0) * 2 + p);
+                }
+#pragma unroll
+            for (uint32_t u = 0; u < CH; u++) {
+                const uint32_t j = jb + 4 * u;
+                if (j < nj) {
+#pragma unroll
+                    for (uint32_t h = 0; h < 2; h++) {
+                        const uint32_t p = lane + 64 * h, k = p >> 1;
+                        bool ne = false;
+                        if (k < nk) {
+                            const uint64_t x = p & 1u ? 0 : tile[k * EG_S + j];
+                            ne = cmp_ne(got[u][h], make_uint4((uint32_t)x, (uint32_t)(x >> 32), 0, 0));
+                        }
+                        const uint64_t who = __ballot(ne);
+                        if (who && lane == (uint32_t)__builtin_ctzll(who)) atomicMin(&low[j], entry0 + k0 + k);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (wave == 0) cmp_report(low, lane, ok, j0, report0, diff, summary);
 }
 
 // Witness bits as packed rows (cw_get_witness_rows*): entry k of the list (w2s points at the range's first entry) of instance
@@ -847,6 +933,21 @@ hipError_t cwk64_egress(hipStream_t s, const void *V, const uint32_t *w2s, uint3
 hipError_t cwk64_egress_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
                            uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t elem_bytes, uint32_t *d_bad) {
     return egress(true, s, V, w2s, n_wit, Bp, 0, n_idx, d_out, elem_bytes, batch, d_idx, d_n_idx, d_bad);
+}
+// The launches of cw64_compare_kernel: the grid and the pieces of the range egress; `image`, `diff` and report0 move with the
+// piece.  elem_bytes = 8 (`image` 8-byte aligned) or 32 (16-byte aligned).
+hipError_t cwk64_compare(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t entry0, uint32_t report0, const void *image, uint32_t elem_bytes, uint32_t *diff, uint32_t *summary) {
+    if (elem_bytes != 8 && elem_bytes != 32) return hipErrorInvalidValue;
+    if (((uintptr_t)image & (elem_bytes == 8 ? 7 : 15)) || (((uintptr_t)diff | (uintptr_t)summary) & 3)) return hipErrorInvalidValue;
+    if (!n_wit) return hipSuccess;
+    const auto kernel = elem_bytes == 8 ? cw64_compare_kernel<8> : cw64_compare_kernel<32>;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + EG_T - 1) / EG_T, (m + 63) / 64), dim3(256), 0, s, (const uint64_t *)V, w2s, n_wit, Bp,
+                           first + done, m, (const uint8_t *)image + (size_t)done * n_wit * elem_bytes, entry0, report0 + done, diff + done,
+                           summary);
+        return hipGetLastError();
+    });
 }
 // packed rows of witness bits: instance tiles in gridDim.x, word tiles of 4 096 entries in gridDim.y: one launch.  `word` (or
 // nullptr) takes an atomicMin of report0 + j for every instance j of the launch that held a value > 1; the caller fills it first.

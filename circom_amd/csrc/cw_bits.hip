@@ -23,6 +23,7 @@
 #include "cw_r1cs_products.h"
 #include "fp256.hip.h"
 #include "cw_list.hip.h"
+#include "cw_compare.hip.h"
 #include "cw_wtns_digest.h"
 
 
@@ -699,6 +700,67 @@ cw_bits_gather_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t l
     }
 }
 
+// Witness compare (cw_compare_witnesses*): the range egress above with its stores turned into loads and compares.  image[j][k]
+// (32 bytes, [count][n_wit]) against the bit of element k of the range (wslot points at its first entry, entry0 in the witness
+// list) in instance first + j: diff[j] = min(diff[j], lowest differing entry0 + k), summary as cw_compare.hip.h states it; the
+// caller fills diff[0 .. count) and summary first.  The tile, the grid and the windows of cw_bits_gather_kernel<false>
+// (bits_gather_window, both table layouts): a wave owns 32 * BITS_GATHER_RUN elements x 64 instances and LOADS whole 1 KiB runs
+// of one instance's row, streaming, every byte of the image requested by exactly one wave.  The expected piece is (bit, 0, 0, 0)
+// on even lanes and zero on odd lanes: an element equals the bit only as the 32-byte value 0 or 1.  Instances past `count` and
+// elements past n_wit neither read nor write.  The windows need no LDS; the 64 words of the reduction are all there is.
+//   fbidx   instance -> position in the side batch or negative (nullptr: no side batch).  An instance the side batch re-ran is
+//           NOT judged from the bit table - its image row is not even read here: cw_kernels.hip cw_compare_kernel with the same
+//           map judges it from the side batch's table, in stream order.
+//   reduce  the lanes of a run cover ascending elements of ONE instance, the runs ascend too: one ballot says whether the wave
+//           found the instance different at all (well-matching images stop there), then the first run with a differing lane
+//           gives the wave's lowest entry, which one lane notes in low[] (one LDS atomic per instance and wave).
+__global__ void __launch_bounds__(256)
+cw_bits_compare_kernel(const uint64_t *__restrict__ T, uint64_t slots, uint32_t lsh, const uint32_t *__restrict__ wslot, uint32_t n_wit,
+                       uint32_t first, uint32_t count, const uint4 *__restrict__ image, uint32_t tiles_fastest, uint32_t entry0,
+                       uint32_t report0, const int32_t *__restrict__ fbidx, uint32_t *__restrict__ diff, uint32_t *__restrict__ summary) {
+    __shared__ uint32_t low[64];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t bk = tiles_fastest ? blockIdx.y : blockIdx.x, bj = tiles_fastest ? blockIdx.x : blockIdx.y;
+    const uint32_t k0 = (bk * 4 + wv) * 32 * BITS_GATHER_RUN;               // this wave's elements
+    const uint32_t j0 = bj * 64;                                             // its 64 instances
+    const uint32_t nj = min(64u, count - j0);
+    if (wv == 0) low[lane] = CMP_EQUAL;
+    __syncthreads();
+    if (k0 < n_wit) {                                                        // (no wave leaves before the barriers)
+        uint64_t win[BITS_GATHER_RUN];                                       // bit jj = the value in instance first + j0 + jj
+        bool have[BITS_GATHER_RUN];
+        bits_gather_window(T, slots, lsh, wslot, n_wit, k0, lane, first + j0, nj, win, have);
+        const uint64_t rerun = __ballot(fbidx && lane < nj && fbidx[first + j0 + lane] >= 0);
+        const bool low_half = !(lane & 1);
+        const uint4 *o = image + ((size_t)j0 * n_wit + k0) * 2 + lane;
+        for (uint32_t jj = 0; jj < nj; jj++, o += (size_t)n_wit * 2) {
+            if ((rerun >> jj) & 1) continue;
+            uint4 w[BITS_GATHER_RUN];
+#pragma unroll
+            for (int r = 0; r < BITS_GATHER_RUN; r++)
+                if (have[r]) w[r] = cmp_load16(o + r * 64);
+            bool ne[BITS_GATHER_RUN], any = false;
+#pragma unroll
+            for (int r = 0; r < BITS_GATHER_RUN; r++) {
+                const uint32_t bit = low_half ? (uint32_t)(win[r] >> jj) & 1u : 0u;
+                ne[r] = have[r] && cmp_ne(w[r], make_uint4(bit, 0u, 0u, 0u));
+                any |= ne[r];
+            }
+            if (__ballot(any)) {
+                uint32_t entry = CMP_EQUAL;
+#pragma unroll
+                for (int r = BITS_GATHER_RUN - 1; r >= 0; r--) {
+                    const uint64_t who = __ballot(ne[r]);
+                    if (who) entry = entry0 + k0 + r * 32 + ((uint32_t)__builtin_ctzll(who) >> 1);
+                }
+                if (lane == 0) atomicMin(&low[jj], entry);
+            }
+        }
+    }
+    __syncthreads();
+    if (wv == 0) cmp_report(low, lane, lane < nj, j0, report0, diff, summary);
+}
+
 // packed main inputs (cw_set_inputs_bits*): masks[group][k] -> bit-table slot input_slot0 + k
 __global__ void __launch_bounds__(256)
 cw_bits_ingest_packed_kernel(const uint64_t *__restrict__ masks, uint64_t *__restrict__ T, uint64_t slots, uint32_t sh, uint32_t input_slot0,
@@ -1323,6 +1385,23 @@ hipError_t cwk_bits_gather(hipStream_t s, const void *T, uint64_t slots, uint32_
 hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t batch,
                               const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t *d_bad) {
     return bits_gather(true, s, T, slots, sh, wslot, n_wit, 0, n_idx, d_out, batch, d_idx, d_n_idx, d_bad);
+}
+// The launches of cw_bits_compare_kernel: the grid and the pieces of the range egress; `image`, `diff` and report0 move with the
+// piece, `fbidx` (or nullptr) is indexed by the batch's instance.
+hipError_t cwk_bits_compare(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t first,
+                            uint32_t count, uint32_t entry0, uint32_t report0, const void *image, const int32_t *fbidx, uint32_t *diff,
+                            uint32_t *summary) {
+    if (!count || !n_wit) return hipSuccess;
+    if (((uintptr_t)image & 15) || (((uintptr_t)diff | (uintptr_t)summary | (uintptr_t)fbidx) & 3)) return hipErrorInvalidValue;
+    const uint32_t kblocks = (n_wit + 128 * BITS_GATHER_RUN - 1) / (128 * BITS_GATHER_RUN);
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        const uint32_t tiles = (m + 63) / 64;
+        const uint32_t tf = tiles >= 8 && kblocks <= 65535u;
+        hipLaunchKernelGGL(cw_bits_compare_kernel, tf ? dim3(tiles, kblocks) : dim3(kblocks, tiles), dim3(256), 0, s, (const uint64_t *)T, slots,
+                           sh, wslot, n_wit, first + done, m, (const uint4 *)image + (size_t)done * n_wit * 2, tf, entry0, report0 + done, fbidx,
+                           diff + done, summary);
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_bits_ingest_packed(hipStream_t s, const void *masks, void *T, uint64_t slots, uint32_t sh, uint32_t input_slot0, uint32_t n_in,
                                   uint32_t batch) {

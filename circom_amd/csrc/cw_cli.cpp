@@ -12,6 +12,14 @@
 //                                                                      "<64 hex digits>  <instance index>", the SHA-256 of the
 //                                                                      .wtns the plain call writes, computed on the device
 //                                                                      (cw_get_wtns_digests); exit codes of the plain call
+//                  cw_witness --compare <name> <input(s).json> <ref.wtns | ref_%d.wtns>
+//                                                                      the same run, no file written: the .wtns of another
+//                                                                      calculator compared byte by byte with what this batch
+//                                                                      computes from the same inputs, on the device
+//                                                                      (cw_compare_wtns_many); one line per instance, "instance
+//                                                                      i: OK" | "instance i: entry k differs" (+ the signal's
+//                                                                      name when <name>.sym exists); exit 0 = all equal, 1 = some
+//                                                                      differ, 2 = usage, I/O (a file that is not the circuit's)
 // <name> is the path prefix of <name>.cwt / <name>.dat / <name>.r1cs (the .r1cs is optional: without it the
 // constraint check is skipped).  Exit code 0 = every instance produced a witness; 1 = at least one failed (the
 // reference aborts on the first failed assert, calcwit/assert_bucket.rs:75-77; here the others are still written).
@@ -22,6 +30,7 @@
 #include <vector>
 
 #include "../../include/circom_amd.h"
+#include "cw_signals.h"
 
 static std::string slurp(const char *path) {
     FILE *f = fopen(path, "rb");
@@ -109,7 +118,87 @@ static int check_files(const std::string &name, char **files, uint32_t n) {
     return bad ? 1 : 0;
 }
 
+// the batch's own witnesses against the files of another calculator: ref (or ref % i) is compared with instance i
+static int compare_files(const std::string &name, const char *input, const char *ref) {
+    cw_circuit *c = nullptr;
+    const std::string r1cs = name + ".r1cs";
+    FILE *probe = fopen(r1cs.c_str(), "rb");
+    if (probe) fclose(probe);
+    CHECK(cw_load((name + ".cwt").c_str(), (name + ".dat").c_str(), probe ? r1cs.c_str() : nullptr, &c));
+    std::vector<uint32_t> list;                                      // the witness list of a simplified system, as below
+    if (FILE *wl = fopen((name + ".w2s").c_str(), "rb")) {
+        uint32_t v;
+        while (fread(&v, 4, 1, wl) == 1) list.push_back(v);
+        fclose(wl);
+        if (!list.empty()) CHECK(cw_set_witness_list(c, list.data(), (uint32_t)list.size()));
+    }
+    const std::vector<std::string> ins = elements(slurp(input));
+    if (ins.empty()) { fprintf(stderr, "no input objects in %s\n", input); return 2; }
+    const uint32_t n = (uint32_t)ins.size();
+    // a pattern as the library's _many calls take it: a % (not %%), an optional width, then d or u
+    bool many = false;
+    for (const char *p = ref; *p && !many; p++)
+        if (*p == '%') {
+            if (p[1] == '%') { p++; continue; }
+            const char *q = p + 1;
+            while (*q >= '0' && *q <= '9') q++;
+            many = *q == 'd' || *q == 'u';
+        }
+    if (!many && n > 1) { fprintf(stderr, "%u inputs need a reference pattern with %%d\n", n); return 2; }
+    const int device = getenv("CW_DEVICE") ? atoi(getenv("CW_DEVICE")) : 0;
+    cw_batch *b = nullptr;
+    CHECK(cw_batch_create(c, device, n, nullptr, &b));
+    for (uint32_t i = 0; i < n; i++) CHECK(cw_set_inputs_json(b, i, ins[i].c_str()));
+    CHECK(cw_run(b));
+    // verdicts are produced whatever the status word says; an instance whose run failed gets a line on stderr beside its verdict
+    std::vector<uint32_t> st(n);
+    CHECK(cw_get_status(b, st.data()));
+    for (uint32_t i = 0; i < n; i++)
+        if (st[i])
+            fprintf(stderr, "instance %u: %s%s(its witness is compared as it stands)\n", i, (st[i] & 1) ? "Failed assert " : "",
+                    (st[i] & 2) ? "division by zero " : "");
+    std::vector<uint32_t> diff(n);
+    uint32_t summary[2] = {0, 0};
+    if (many) CHECK(cw_compare_wtns_many(b, 0, n, ref, diff.data(), summary));
+    else CHECK(cw_compare_wtns(b, 0, ref, diff.data()));
+    // entry k of the witness is signal list[k] of a simplified system and signal k otherwise (how this project's writers number
+    // the witness); its name comes from <name>.sym through the walk cw_explain makes
+    std::vector<std::string> names;
+    {
+        std::vector<uint8_t> buf;
+        if (FILE *sp = fopen((name + ".sym").c_str(), "rb")) {
+            char chunk[1 << 16];
+            size_t got;
+            while ((got = fread(chunk, 1, sizeof chunk, sp)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+            fclose(sp);
+            names.assign(cw_n_signals(c), std::string());
+            cwsig::sym_walk(buf, [&](unsigned long sid, const std::string &nm) {
+                if (sid < names.size()) names[sid] = nm;
+            });
+        }
+    }
+    int differ = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (diff[i] == 0xFFFFFFFFu) { printf("instance %u: OK\n", i); continue; }
+        differ++;
+        const uint32_t sid = list.empty() ? diff[i] : (diff[i] < list.size() ? list[diff[i]] : 0xFFFFFFFFu);
+        if (sid == 0) printf("instance %u: entry %u differs (one)\n", i, diff[i]);
+        else if (sid < names.size() && !names[sid].empty()) printf("instance %u: entry %u differs (%s)\n", i, diff[i], names[sid].c_str());
+        else printf("instance %u: entry %u differs\n", i, diff[i]);
+    }
+    cw_batch_free(b);
+    cw_free(c);
+    return differ ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--compare")) {
+        if (argc != 5) {
+            fprintf(stderr, "Usage: %s --compare <circuit path prefix> <input(s).json> <ref.wtns | ref_%%d.wtns>\n", argv[0]);
+            return 2;
+        }
+        return compare_files(argv[2], argv[3], argv[4]);
+    }
     if (argc >= 2 && !strcmp(argv[1], "--check")) {
         if (argc < 4) {
             fprintf(stderr, "Usage: %s --check <circuit path prefix> <a.wtns> [<b.wtns> ...]\n", argv[0]);
@@ -120,7 +209,8 @@ int main(int argc, char **argv) {
     const bool sha = argc == 4 && !strcmp(argv[1], "--sha256");
     if (argc != 4) {
         fprintf(stderr, "Usage: %s <circuit path prefix> <input.json> <output.wtns | out_%%d.wtns>\n"
-                        "       %s --sha256 <circuit path prefix> <input.json>\n", argv[0], argv[0]);
+                        "       %s --sha256 <circuit path prefix> <input.json>\n"
+                        "       %s --compare <circuit path prefix> <input(s).json> <ref.wtns | ref_%%d.wtns>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string name = sha ? argv[2] : argv[1];

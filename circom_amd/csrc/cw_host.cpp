@@ -30,6 +30,7 @@
 #include "cw_signals.h"
 #include "cw_fn64.h"
 #include "cw_wtns_read.h"
+#include "cw_compare.h"
 
 typedef unsigned __int128 u128;
 
@@ -4333,6 +4334,181 @@ extern "C" int cw_read_wtns_many(cw_batch *b, uint32_t first, uint32_t count, co
     if (int rc = check_file_pattern(pattern)) return rc;
     if (int rc = supply_args(b, first, count, pattern, 1)) return rc;
     return read_wtns_files(b, first, count, pattern, true);
+}
+
+// ---- witness compare (cw_compare.h) ----
+// An image of witnesses, image[j][k] = entry entry0 + k of instance first + j, eb bytes per element, against what the egress would
+// write there: d_diff[j] = the lowest differing entry, d_sum = {instances that differ, the lowest of them} (d_sum may be null);
+// both are filled by the caller.  One kernel per table layout (cw_kernels.h), walking the engines as at_egress does:
+//   64-bit runtime     cw64_compare_kernel<EB>, both element sizes - also in the supplied-witness state
+//   bit-plane batches  cw_bits_compare_kernel on the bit table, which skips the instances the side batch re-ran, then ONE launch of
+//                      cw_compare_kernel<MONT> on the side batch's table with the instance -> side-batch map judges those; a side
+//                      batch that holds the whole batch answers alone.  The first call after a cw_run waits for bits_resolve.
+//   256-bit schedule   cw_compare_kernel<MONT>, canonical and Montgomery-form tables
+// `report0`: the caller's number of the launch's first instance (summary[1] speaks in the caller's numbering).
+static int compare_launch(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, uint32_t report0, const void *d_image,
+                          uint32_t eb, uint32_t *d_diff, uint32_t *d_sum) {
+    const cw_circuit *c = b->c;
+    if (c->is64) {
+        HIPCHK(cwk64_compare(b->stream, b->d_V64, b->d_w2s + entry0, n, b->Bp, first, count, entry0, report0, d_image, eb, d_diff, d_sum));
+        return CW_OK;
+    }
+    if (b->bitmode) {
+        if (int rc = bits_resolve(b)) return rc;
+        // The kernels do atomics on words the caller filled on b->stream just before: the side batch must launch behind those
+        // fills.  bits_resolve creates it on the parent's stream (batch_create_impl(c, device, n, b->stream, ..)); checked here
+        // because this is the first caller that depends on it.
+        if (b->fb && b->fb->stream != b->stream) return fail(CW_ESTATE, "the side batch does not share its parent's stream");
+        if (b->fb && b->fb_inst.size() == b->batch) return compare_launch(b->fb, entry0, n, first, count, report0, d_image, eb, d_diff, d_sum);
+        const bool side = b->fb && !b->fb_inst.empty();
+        if (side)
+            if (int rc = fb_map(b)) return rc;
+        HIPCHK(cwk_bits_compare(b->stream, b->d_T, b->bits_slots, b->bits_sh, b->d_wslot + entry0, n, first, count, entry0, report0, d_image,
+                                side ? (const int32_t *)b->d_fbindex.get() : nullptr, d_diff, d_sum));
+        if (side)
+            HIPCHK(cwk_compare(b->stream, b->fb->d_V, b->fb->d_w2s + entry0, n, b->fb->Bp, first, count, entry0, report0, d_image,
+                               (const int32_t *)b->d_fbindex.get(), b->batch, (uint32_t)b->fb_inst.size(), d_diff, d_sum, b->fb->c->mont,
+                               b->fb->c->P));
+        return CW_OK;
+    }
+    HIPCHK(cwk_compare(b->stream, b->d_V, b->d_w2s + entry0, n, b->Bp, first, count, entry0, report0, d_image, nullptr, 0, 0, d_diff, d_sum,
+                       c->mont, c->P));
+    return CW_OK;
+}
+// what every form checks first, in the order of the other getters: null / ranges / alignments (CW_EINVAL), the device, the state
+static int compare_ready(cw_batch *b, const void *image, const void *diff, const void *summary, uint32_t entry0, uint32_t n, uint32_t first,
+                         uint32_t count, uint32_t eb, bool device, const char *who) {
+    if (!b || !image || !diff) return fail(CW_EINVAL, "null argument");
+    const char *why = cwcmp::check_range(entry0, n, b->c->n_witness, first, count, b->batch);
+    if (!why && device) why = cwcmp::check_device(image, diff, summary, eb);
+    if (why) return fail(CW_EINVAL, std::string(who) + ": " + why);
+    return list_state(b, who);
+}
+static int compare_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const void *d_image, void *d_diff,
+                          void *d_summary, uint32_t eb, const char *who) {
+    if (int rc = compare_ready(b, d_image, d_diff, d_summary, entry0, n, first, count, eb, true, who)) return rc;
+    uint32_t *d_sum = (uint32_t *)d_summary;
+    if (d_sum) {
+        HIPCHK(cwk_fill32(b->stream, d_sum, 0u, 1));
+        HIPCHK(cwk_fill32(b->stream, d_sum + 1, cwcmp::EQUAL, 1));
+    }
+    HIPCHK(cwk_fill32(b->stream, (uint32_t *)d_diff, cwcmp::EQUAL, count));
+    if (n == 0 || count == 0) return CW_OK;
+    return compare_launch(b, entry0, n, first, count, first, d_image, eb, (uint32_t *)d_diff, d_sum);
+}
+// Host image, host verdicts, after compare_ready: pieces of whole rows go through the staging buffer (cw_pieces, as
+// get_witnesses_host does), the piece's verdict words and the summary behind its rows.  Synchronised before the staging buffer is
+// written again and before returning.
+static int compare_staged(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image, uint32_t *diff,
+                          uint32_t summary[2], uint32_t eb) {
+    if (summary) cwcmp::clear(summary);
+    if (count == 0) return CW_OK;
+    if (n == 0) {
+        std::fill(diff, diff + count, cwcmp::EQUAL);
+        return CW_OK;
+    }
+    const size_t row = (size_t)n * eb;
+    const uint32_t per = cwcmp::piece_rows(row, count);
+    HIPCHK(b->d_bulk.grow(cwcmp::staging_bytes(row, per)));
+    uint32_t *d_diff = (uint32_t *)((char *)b->d_bulk.get() + cwcmp::diff_offset(row, per));
+    uint32_t *d_sum = (uint32_t *)((char *)b->d_bulk.get() + cwcmp::summary_offset(row, per));
+    HIPCHK(cwk_fill32(b->stream, d_sum, 0u, 1));
+    HIPCHK(cwk_fill32(b->stream, d_sum + 1, cwcmp::EQUAL, 1));
+    const int rc = cw_pieces(count, per, [&](uint32_t done, uint32_t m) {
+        HIPCHK(hipMemcpyAsync(b->d_bulk, cwcmp::piece_at(image, row, done), (size_t)m * row, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(cwk_fill32(b->stream, d_diff, cwcmp::EQUAL, m));
+        if (int rc2 = compare_launch(b, entry0, n, first + done, m, first + done, b->d_bulk, eb, d_diff, d_sum)) return rc2;
+        HIPCHK(hipMemcpyAsync(diff + done, d_diff, (size_t)m * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return CW_OK;
+    });
+    if (rc) return rc;
+    if (summary) {
+        HIPCHK(hipMemcpyAsync(summary, d_sum, 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return CW_OK;
+}
+static int compare_host(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image, uint32_t *diff,
+                        uint32_t summary[2], uint32_t eb, const char *who) {
+    if (int rc = compare_ready(b, image, diff, summary, entry0, n, first, count, eb, false, who)) return rc;
+    return compare_staged(b, entry0, n, first, count, image, diff, summary, eb);
+}
+extern "C" int cw_compare_witnesses(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image,
+                                    uint32_t *diff, uint32_t summary[2]) {
+    return compare_host(b, entry0, n, first, count, image, diff, summary, 32, "cw_compare_witnesses");
+}
+extern "C" int cw_compare_witnesses_n8(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image,
+                                       uint32_t *diff, uint32_t summary[2]) {
+    if (b && !b->c->is64) return cw_compare_witnesses(b, entry0, n, first, count, image, diff, summary);
+    return compare_host(b, entry0, n, first, count, image, diff, summary, 8, "cw_compare_witnesses_n8");
+}
+extern "C" int cw_compare_witnesses_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const void *d_image,
+                                           void *d_diff, void *d_summary) {
+    return compare_device(b, entry0, n, first, count, d_image, d_diff, d_summary, 32, "cw_compare_witnesses_device");
+}
+extern "C" int cw_compare_witnesses_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const void *d_image,
+                                              void *d_diff, void *d_summary) {
+    if (b && !b->c->is64) return cw_compare_witnesses_device(b, entry0, n, first, count, d_image, d_diff, d_summary);
+    return compare_device(b, entry0, n, first, count, d_image, d_diff, d_summary, 8, "cw_compare_witnesses_device_n8");
+}
+// .wtns files against the batch: every file through cw_wtns_parse, exactly as read_wtns_files reads it (a file that is not the
+// circuit's is CW_EIO with the path and the reason, not a difference); the bodies of a piece are collected in a host image and
+// compared as one staged image - not one launch per file.  Checked in the order of cw_read_wtns: arguments, files, device, state.
+static int compare_wtns_files(cw_batch *b, uint32_t first, uint32_t count, const char *pattern, bool is_pattern, uint32_t *diff,
+                              uint32_t summary[2], const char *who) {
+    const cw_circuit *c = b->c;
+    const uint32_t n8 = cw_element_bytes(c);
+    const size_t row = (size_t)c->n_witness * n8;
+    const uint32_t per = cwcmp::piece_rows(row, count);
+    std::vector<uint8_t> img((size_t)per * row), file;
+    uint32_t total[2], part[2];
+    cwcmp::clear(total);
+    // file `at` of the range, read and checked; its body goes to dst when there is one
+    auto load = [&](uint32_t at, uint8_t *dst) {
+        char path[4096];
+        if (is_pattern) snprintf(path, sizeof path, pattern, first + at);
+        else snprintf(path, sizeof path, "%s", pattern);
+        if (!read_file(path, file)) return fail(CW_EIO, std::string("cannot read: ") + path);
+        const uint8_t *body = nullptr;
+        if (const char *why = cw_wtns_parse(file.data(), file.size(), n8, (const uint8_t *)c->q.w, c->n_witness, &body))
+            return fail(CW_EIO, std::string(path) + ": " + why);
+        if (dst) memcpy(dst, body, row);
+        return (int)CW_OK;
+    };
+    // a range of several pieces (more than 256 MiB of bodies): EVERY file is checked before the device and the state are looked
+    // at, in the order of the instances, so the files are read twice; a range of one piece reads each file once
+    if (count > per)
+        for (uint32_t at = 0; at < count; at++)
+            if (int rc2 = load(at, nullptr)) return rc2;
+    const int rc = cw_pieces(count, per, [&](uint32_t done, uint32_t n) {
+        for (uint32_t k = 0; k < n; k++)
+            if (int rc2 = load(done + k, &img[(size_t)k * row])) return rc2;
+        if (int rc2 = list_state(b, who)) return rc2;
+        if (int rc2 = compare_staged(b, 0, c->n_witness, first + done, n, img.data(), diff + done, summary ? part : nullptr, n8)) return rc2;
+        if (summary) cwcmp::merge(total, part);
+        return CW_OK;
+    });
+    if (rc) return rc;
+    if (summary) memcpy(summary, total, 8);
+    return CW_OK;
+}
+extern "C" int cw_compare_wtns(cw_batch *b, uint32_t instance, const char *path, uint32_t *diff) {
+    if (!b || !path || !diff) return fail(CW_EINVAL, "null argument");
+    if (instance >= b->batch) return fail(CW_EINVAL, "cw_compare_wtns: instance range out of the batch");
+    return compare_wtns_files(b, instance, 1, path, false, diff, nullptr, "cw_compare_wtns");
+}
+// `pattern`: a printf pattern with exactly one %u / %d (the instance number), as cw_write_wtns_many takes it
+extern "C" int cw_compare_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern, uint32_t *diff, uint32_t summary[2]) {
+    if (!b || !pattern || !diff) return fail(CW_EINVAL, "null argument");
+    if ((uint64_t)first + count > b->batch) return fail(CW_EINVAL, "cw_compare_wtns_many: instance range out of the batch");
+    if (int rc = check_file_pattern(pattern)) return rc;
+    if (count == 0) {
+        if (int rc = list_state(b, "cw_compare_wtns_many")) return rc;
+        if (summary) cwcmp::clear(summary);
+        return CW_OK;
+    }
+    return compare_wtns_files(b, first, count, pattern, true, diff, summary, "cw_compare_wtns_many");
 }
 
 // Debug trace of one instance (the reference prints template, line and the component trace of a failed `===` and

@@ -144,6 +144,24 @@ hipError_t cwk_bits_gather_at(hipStream_t s, const void *T, uint64_t slots, uint
                               const uint32_t *d_idx, uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t *d_bad);
 hipError_t cwk64_egress_at(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t batch, const uint32_t *d_idx,
                            uint32_t n_idx, const uint32_t *d_n_idx, void *d_out, uint32_t elem_bytes, uint32_t *d_bad);
+// witness compare (cw_compare_witnesses*, cw_compare.h): the range egress kernel of each table layout with its store turned into
+// a streaming load and a compare.  image[j][k] = entry k of the range (wslot / w2s point at its first entry, which is entry0 of
+// the witness list) of instance first + j, [count][n_wit] elements of 32 bytes (16-byte aligned) or, cwk64_compare with
+// elem_bytes = 8, 8 bytes (8-byte aligned).  diff[j] takes atomicMin(lowest differing entry0 + k); the workgroup that finds
+// 0xFFFFFFFF there counts the instance: summary[0] += 1, summary[1] = min(.., report0 + j) (`summary` may be nullptr).  The
+// caller fills diff[0 .. count) with 0xFFFFFFFF and summary with {0, 0xFFFFFFFF} first.
+//   cwk_compare        with `remap` (n_remap entries, indexed by first + j) the kernel reads column remap[first + j] < limit of its
+//                      table and leaves alone the positions whose entry is negative: the instances a bit-plane batch re-ran,
+//                      judged from the side batch's table
+//   cwk_bits_compare   with `fbidx` (the same map) those instances are skipped: they are not judged from the bit table
+hipError_t cwk_compare(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                       uint32_t entry0, uint32_t report0, const void *image, const int32_t *remap, uint32_t n_remap, uint32_t limit,
+                       uint32_t *diff, uint32_t *summary, bool mont, const FpParams &P);
+hipError_t cwk_bits_compare(hipStream_t s, const void *T, uint64_t slots, uint32_t sh, const uint32_t *wslot, uint32_t n_wit, uint32_t first,
+                            uint32_t count, uint32_t entry0, uint32_t report0, const void *image, const int32_t *fbidx, uint32_t *diff,
+                            uint32_t *summary);
+hipError_t cwk64_compare(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                         uint32_t entry0, uint32_t report0, const void *image, uint32_t elem_bytes, uint32_t *diff, uint32_t *summary);
 hipError_t cwk_bits_r1cs(hipStream_t s, const void *erecs, uint32_t n_evrows, const uint32_t *chunk, uint32_t n_chunks,
                          const uint32_t *terms, const uint32_t *ctab, const uint32_t *row_orig, const uint32_t *ichunk,
                          uint32_t n_ichunks, const uint32_t *iterms, const uint32_t *itab, const uint32_t *irow_orig, const void *T,

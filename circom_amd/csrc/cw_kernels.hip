@@ -14,6 +14,7 @@
 #include "cw_select.h"
 #include "cw_columns.hip.h"
 #include "cw_list.hip.h"
+#include "cw_compare.hip.h"
 #include "cw_wtns_digest.h"
 
 #define CW_BLOCK 256
@@ -1083,6 +1084,77 @@ cw_gather_many_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ 
     }
 }
 
+// ---- witness compare (cw_compare_witnesses*): the range egress above with its store turned into a load and a compare ----
+// image[j][k] (32 bytes, [count][n_wit]) against entry k of the range (w2s points at its first entry, entry0 in the witness list)
+// of instance first + j: diff[j] = min(diff[j], lowest differing entry0 + k), summary as cw_compare.hip.h states it; the caller
+// fills diff[0 .. count) and summary first.  The tile, the stage (MONT: fe_out_of_mont on the way) and the address pattern of
+// cw_gather_many_kernel<MONT, false>: a workgroup owns 64 instances x GM_TILE entries, lane = instance for the table read, and
+// where the egress stores, each lane LOADS its 16-byte piece of the image - 2 GM_TILE consecutive pieces = 512 bytes of one
+// instance's row per half wave, every byte of the image requested by exactly one workgroup, streaming - and compares it, after
+// the barrier, with its piece of the tile.  The eight loads of a lane are issued before the stage: they are in flight while the
+// table is read and converted.  Lanes past `count` and entries past n_wit neither read nor write; nothing is read behind the image.
+//   remap   with a table `remap` of n_remap entries the lane reads column remap[first + j] of THIS table (an entry must be below
+//           `limit`), and a position whose entry is negative is LEFT ALONE, neither read nor judged: this is how the instances
+//           a bit-plane batch re-ran are judged from the side batch's table in one launch, behind cw_bits_compare_kernel (which
+//           skips them).  The lanes of a wave are the same 64 instances in every wave: a ballot of `ok` is the tile's keep mask.
+//   reduce  a half wave covers the GM_TILE entries of one instance in ascending order: after a ballot the lowest differing lane
+//           of a half notes its entry in low[] (one LDS atomic per instance and store-loop step, none for equal pieces).
+template <bool MONT>
+__global__ void __launch_bounds__(256)
+cw_compare_kernel(const uint4 *__restrict__ V, const uint32_t *__restrict__ w2s, uint32_t n_wit, uint32_t Bp, uint32_t first,
+                  uint32_t count, const uint4 *__restrict__ image, FpParams P, uint32_t entry0, uint32_t report0,
+                  const int32_t *__restrict__ remap, uint32_t n_remap, uint32_t limit, uint32_t *__restrict__ diff,
+                  uint32_t *__restrict__ summary) {
+    __shared__ uint4 tile[GM_TILE][2][65];
+    __shared__ uint32_t low[64];
+    const uint32_t k0 = blockIdx.x * GM_TILE, i0 = blockIdx.y * 64;
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;  // 4 waves
+    const bool live = i0 + lane < count;
+    uint32_t inst = first + i0 + lane;
+    bool ok = live;
+    if (remap) {
+        const int32_t r = live && inst < n_remap ? remap[inst] : -1;
+        ok = r >= 0 && (uint32_t)r < limit;
+        inst = (uint32_t)r;
+    }
+    const uint64_t keep = __ballot(ok);
+    if (wv == 0) low[lane] = CMP_EQUAL;
+    // this lane's pieces of the image, one per step of the compare loop: they do not depend on the tile, so all of them are in
+    // flight while the table is read and converted
+    constexpr uint32_t PIECES = 2 * GM_TILE, PER = 64 / PIECES, STEPS = 64 / (4 * PER);
+    static_assert(PER == 2, "the reduction below takes the two halves of a wave for two instances");
+    const uint32_t piece = lane % PIECES, sub = lane / PIECES, pe = piece >> 1, h = piece & 1;
+    const uint32_t pk = k0 + pe;
+    uint4 got[STEPS];
+#pragma unroll
+    for (uint32_t u = 0; u < STEPS; u++) {
+        const uint32_t ii = wv * PER + sub + u * 4 * PER;
+        got[u] = make_uint4(0, 0, 0, 0);
+        if (pk < n_wit && ((keep >> ii) & 1)) got[u] = cmp_load16(&image[((size_t)(i0 + ii) * n_wit + pk) * 2 + h]);
+    }
+    for (uint32_t e = wv; e < GM_TILE; e += 4) {
+        const uint32_t k = k0 + e;
+        if (k < n_wit && ok) {
+            const size_t base = (size_t)w2s[k] * 2 * Bp + inst;
+            uint4 lo = V[base], hi = V[base + Bp];
+            if (MONT) fe_out_of_mont(lo, hi, P);
+            tile[e][0][lane] = lo;
+            tile[e][1][lane] = hi;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t u = 0; u < STEPS; u++) {
+        const uint32_t ii = wv * PER + sub + u * 4 * PER;
+        const bool ne = pk < n_wit && ((keep >> ii) & 1) && cmp_ne(got[u], tile[pe][h][ii]);
+        const uint64_t who = __ballot(ne);
+        const uint32_t mine = (uint32_t)(sub ? who >> 32 : who);
+        if (mine && piece == (uint32_t)__builtin_ctz(mine)) atomicMin(&low[ii], entry0 + pk);
+    }
+    __syncthreads();
+    if (wv == 0) cmp_report(low, lane, live, i0, report0, diff, summary);
+}
+
 // ---- witness bits as packed rows (cw_get_witness_rows*) -----------------------------------------------------
 // Entry k of the list (w2s points at the range's first entry) of instance first + j becomes bit k & 63 of word k >> 6 of rows[j]
 // (MSB: the bits of each byte the other way round), 1 if and only if the value is 1.  The shape of the 64-bit runtime's kernel
@@ -1694,6 +1766,20 @@ hipError_t cwk_gather_at(hipStream_t s, const void *V, const uint32_t *w2s, uint
                          uint32_t n_idx, const uint32_t *d_n_idx, const int32_t *remap, uint32_t n_remap, void *d_out, uint32_t *d_bad,
                          bool mont, const FpParams &P) {
     return gather_many(true, s, V, w2s, n_wit, Bp, 0, n_idx, d_out, mont, P, batch, d_idx, d_n_idx, remap, n_remap, remap ? nullptr : d_bad);
+}
+// The launches of cw_compare_kernel: the grid and the pieces of the range egress; `image`, `diff` and report0 move with the piece.
+hipError_t cwk_compare(hipStream_t s, const void *V, const uint32_t *w2s, uint32_t n_wit, uint32_t Bp, uint32_t first, uint32_t count,
+                       uint32_t entry0, uint32_t report0, const void *image, const int32_t *remap, uint32_t n_remap, uint32_t limit,
+                       uint32_t *diff, uint32_t *summary, bool mont, const FpParams &P) {
+    if (!count || !n_wit) return hipSuccess;
+    if (((uintptr_t)image & 15) || (((uintptr_t)diff | (uintptr_t)summary | (uintptr_t)remap) & 3)) return hipErrorInvalidValue;
+    const auto kernel = mont ? cw_compare_kernel<true> : cw_compare_kernel<false>;
+    return cw_pieces(count, 65535u * 64u, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(kernel, dim3((n_wit + GM_TILE - 1) / GM_TILE, (m + 63) / 64), dim3(256), 0, s, (const uint4 *)V, w2s, n_wit, Bp,
+                           first + done, m, (const uint4 *)image + (size_t)done * n_wit * 2, P, entry0, report0 + done, remap, n_remap, limit,
+                           diff + done, summary);
+        return hipGetLastError();
+    });
 }
 hipError_t cwk_mulbench(hipStream_t s, const void *a, const void *b, void *out, uint32_t n, uint32_t iters,
                         const FpParams &P) {

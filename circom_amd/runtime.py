@@ -33,7 +33,7 @@ CLI_PATH = _HERE / "bin" / "cw_witness"     # process-level drop-in (csrc/cw_cli
 def build_library(force: bool = False) -> Path:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [_HERE / "csrc" / n for n in ("cw_kernels.hip", "cw_bits.hip", "cw64.hip", "cw_host.cpp", "cw_cli.cpp", "cw_kernels.h",
-                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_signals.h", "cw_fn64.h", "cw_wtns_read.h", "cw_wtns_digest.h", "cw_sha256.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
+                                         "cw_tape.h", "cw_r1cs_plan.h", "cw_bits_host.h", "cw_bits_layout.h", "cw_devbuf.h", "cw_rerun.h", "cw_pieces.h", "cw_rows.h", "cw_columns.h", "cw_columns.hip.h", "cw_select.h", "cw_signals.h", "cw_fn64.h", "cw_wtns_read.h", "cw_compare.h", "cw_compare.hip.h", "cw_wtns_digest.h", "cw_sha256.h", "fp256.hip.h", "cw_rowops.hip.h", "cw_list.hip.h", "cw_call.hip.h")]
     outs = [LIB_PATH, CLI_PATH]
     if not force and all(o.exists() and all(o.stat().st_mtime >= s.stat().st_mtime for s in srcs) for o in outs):
         return LIB_PATH
@@ -132,6 +132,12 @@ _SIGS = {
     "cw_get_witnesses_at_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cw_get_wtns_digests": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "cw_get_wtns_digests_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "cw_compare_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_compare_witnesses_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_compare_witnesses_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_compare_witnesses_device_n8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cw_compare_wtns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p]),
+    "cw_compare_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]),
     "cw_write_wtns_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p]),
     "cw_write_wtnsb": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cw_set_witnesses": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -669,6 +675,50 @@ class Batch:
         """the same into device memory: [count][32] at dptr, 16-byte aligned; asynchronous on the batch's stream
         (cw_get_wtns_digests_device)"""
         _chk(lib().cw_get_wtns_digests_device(self.h, first, count, C.c_void_p(dptr)))
+
+    def compare_witnesses(self, image, entry0: int = 0, first: int = 0):
+        """an image of witnesses against the batch, on the device (cw_compare_witnesses(_n8)): image is uint8 [count][n][eb], eb =
+        32 or circuit.element_bytes, image[j][k] = entry entry0 + k of instance first + j.  Returns (diff, n_diff, lowest): diff
+        uint32 [count], the lowest entry whose bytes differ from what the egress would write or 0xFFFFFFFF; n_diff the instances
+        that differ; lowest the first of them (first + j) or 0xFFFFFFFF"""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] not in (32, self.circuit.element_bytes):
+            raise ValueError("image must be [count][n][32] or [count][n][element_bytes] bytes")
+        count, n, eb = image.shape
+        diff = np.zeros(count, dtype=np.uint32)
+        summary = np.zeros(2, dtype=np.uint32)
+        # (an empty array has no address worth passing: the library refuses a null pointer before it looks at the ranges)
+        spare = C.create_string_buffer(8)
+        iptr = image.ctypes.data_as(C.c_void_p) if image.size else C.cast(spare, C.c_void_p)
+        dptr = diff.ctypes.data_as(C.c_void_p) if diff.size else C.cast(spare, C.c_void_p)
+        fn = lib().cw_compare_witnesses if eb == 32 else lib().cw_compare_witnesses_n8
+        _chk(fn(self.h, entry0, n, first, count, iptr, dptr, summary.ctypes.data_as(C.c_void_p)))
+        return diff, int(summary[0]), int(summary[1])
+
+    def compare_witnesses_device(self, d_image: int, d_diff: int, first: int, count: int, entry0: int = 0, n: int | None = None,
+                                 d_summary: int | None = None, n8: bool = False) -> None:
+        """the same from device memory into device memory: [count][n][32] at d_image (16-byte aligned) or, n8=True,
+        [count][n][circuit.element_bytes]; d_diff: count uint32; d_summary: 0 / None or the address of two uint32.  The call fills
+        and writes both itself, in stream order; asynchronous on the batch's stream (cw_compare_witnesses_device(_n8))"""
+        n = self.circuit.n_witness - entry0 if n is None else n
+        fn = lib().cw_compare_witnesses_device_n8 if n8 else lib().cw_compare_witnesses_device
+        _chk(fn(self.h, entry0, n, first, count, C.c_void_p(d_image), C.c_void_p(d_diff), C.c_void_p(d_summary) if d_summary else None))
+
+    def compare_wtns(self, instance: int, path) -> int:
+        """one .wtns file against instance `instance`: the lowest differing entry or 0xFFFFFFFF (cw_compare_wtns); a file that is
+        not the circuit's raises CwError (CW_EIO) with the path and the reason"""
+        diff = C.c_uint32(0)
+        _chk(lib().cw_compare_wtns(self.h, instance, os.fsencode(str(path)), C.byref(diff)))
+        return diff.value
+
+    def compare_wtns_many(self, first: int, count: int, pattern: str):
+        """the files pattern % (first + j) against the instances of the range (cw_compare_wtns_many): (diff, n_diff, lowest) as
+        compare_witnesses returns them"""
+        diff = np.zeros(max(count, 0), dtype=np.uint32)
+        summary = np.zeros(2, dtype=np.uint32)
+        dptr = diff.ctypes.data_as(C.c_void_p) if diff.size else C.cast(C.create_string_buffer(8), C.c_void_p)
+        _chk(lib().cw_compare_wtns_many(self.h, first, count, os.fsencode(str(pattern)), dptr, summary.ctypes.data_as(C.c_void_p)))
+        return diff, int(summary[0]), int(summary[1])
 
     def device_values(self):
         """(device pointer, bytes, padded batch) of the value table (cw_device_values; layout: include/circom_amd.h)"""

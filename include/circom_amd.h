@@ -576,6 +576,68 @@ int cw_get_witnesses_at_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, cons
  *   not here     an index-list form; one message split over lanes; other hash functions. */
 int cw_get_wtns_digests(cw_batch *b, uint32_t first, uint32_t count, uint8_t *out);
 int cw_get_wtns_digests_device(cw_batch *b, uint32_t first, uint32_t count, void *d_out);
+/* ---- witness compare: an image or .wtns files against the batch, on the device, every engine ---------------------------------
+ * This project states correctness as byte equality with another calculator's `.wtns`.  These calls apply that measure to a whole
+ * batch where the table lies: the table is read once, the image once, four bytes per instance are written, and the first
+ * differing entry is named - which a digest cannot do.  Witness programs are deterministic, so "equal to what this batch computes
+ * from the same inputs" is the verdict on another calculator's witnesses for every engine (cw_set_witnesses* serves the 64-bit
+ * runtime only); one batch's cw_get_witnesses_device image is another batch's compare image (emitted code against the
+ * interpreter, the bit-plane program against the 256-bit schedule).
+ *   image        image[j][k]: entry entry0 + k of the witness list (cw_set_witness_list order, as every egress) of instance
+ *                first + j, j < count, k < n.  Dense: count x n elements, offsets in 64-bit arithmetic.
+ *   element      32 bytes, or cw_element_bytes in the _n8 forms (8 for the 64-bit runtime; for every other circuit they ARE the
+ *                32-byte calls).
+ *   verdict      diff[j] = the lowest entry0 + k for which the element's bytes in the image differ from the bytes
+ *                cw_get_witnesses_device(_n8) would write there at that moment; 0xFFFFFFFF: the run is equal.  BYTES are compared,
+ *                nothing is reduced or repaired: an image value v + q differs from v; in the 32-byte form of the 64-bit runtime
+ *                the upper 24 bytes must be zero; for a bit-plane batch an element equals the bit only as the 32-byte value 0 or
+ *                1.  A table of Montgomery forms is converted on the way, as every egress does.  Verdicts are produced whatever
+ *                the status word says, as the file and digest calls do.
+ *   summary      optional.  summary[0] = the instances of the range with a difference, each counted once; summary[1] = the
+ *                lowest of them as first + j, or 0xFFFFFFFF.
+ *   errors       in the order of the other getters: a null batch, image or diff; entry0 + n > cw_n_witness or first + count >
+ *                batch (no 32-bit wrap); device form: d_image not aligned to 16 bytes (8 bytes for the 8-byte element), d_diff or
+ *                d_summary not to 4 (the pointers are not touched): CW_EINVAL.  Then the device (a host-only batch: CW_EDEVICE),
+ *                then the state: CW_ESTATE "... before cw_run" for a batch that has neither run nor been supplied, "witnesses
+ *                missing for N instances" for a supplied table with gaps; a complete supplied table is served.
+ *   empty        count == 0: CW_OK, diff is not written, summary becomes {0, 0xFFFFFFFF}.  n == 0 with count > 0:
+ *                diff[0 .. count) becomes 0xFFFFFFFF.
+ *   lifetime     the device form launches INSIDE the call and writes d_diff[0 .. count) and d_summary itself, in stream order: a
+ *                fill, then the compare.  The image is read in stream order and may be reused once the batch's stream has passed
+ *                the call.  Asynchronous - with the one exception of every device egress: the first call after a cw_run of a
+ *                bit-plane batch waits for the evaluation.  The host form stages pieces of whole rows in the batch's bulk buffer
+ *                (the piece's verdict words behind them) and synchronises before it returns.  The calls only read the table:
+ *                status words, first-bad rows, the timing marks, a captured cw_run_check graph and the supplied state stay as
+ *                they were; before or after cw_check_r1cs.
+ *   files        cw_compare_wtns / _many: each file goes through the checked reader of cw_read_wtns (csrc/cw_wtns_read.h): a wrong
+ *                magic, version, n8, prime, witness length or body size is CW_EIO with the path and the reason - NOT a
+ *                difference.  Only the bodies are compared, entry0 = 0 and n = cw_n_witness, the element the files carry.
+ *                `pattern` has one %u or %d, as cw_write_wtns_many.  Many files go to the device as one staged image per piece,
+ *                not one launch per file.  Checked in the order of cw_read_wtns: arguments, files, device, state - a host-only
+ *                batch can tell a good file from a bad one.
+ *   memory       the staging buffer of the host forms is the batch's bulk buffer; a bit-plane batch uploads its instance ->
+ *                side-batch map (4 bytes per instance) with the first call after a resolve.  A batch that never asks pays nothing.
+ *   engines      one kernel per table layout, each the range egress kernel with its store turned into a streaming load and a
+ *                compare: lane = instance for the table read, the tile turned through LDS (a ballot window on the bit table),
+ *                the image read in 512 B to 1 KiB contiguous pieces of one instance's row, every byte by exactly one workgroup.
+ *                64-bit runtime (csrc/cw64.hip cw64_compare_kernel<EB>, also in the supplied-witness state), 256-bit schedule
+ *                (csrc/cw_kernels.hip cw_compare_kernel<MONT>, canonical and Montgomery-form tables), bit-plane batches
+ *                (csrc/cw_bits.hip cw_bits_compare_kernel, both table layouts; the instances the 256-bit side batch re-ran are
+ *                skipped there and judged from the side batch's table in one launch).  The mismatches of a workgroup are reduced
+ *                in LDS first (csrc/cw_compare.hip.h): at most one global atomicMin per instance and workgroup, none for an image
+ *                that matches; the workgroup that sees 0xFFFFFFFF come back counts the instance.
+ *   not here     an index-list form; narrow elements; big-endian images; putting the image INTO the table (that remains
+ *                cw_set_witnesses*, 64-bit runtime only). */
+int cw_compare_witnesses(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image, uint32_t *diff,
+                         uint32_t summary[2]);
+int cw_compare_witnesses_n8(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const uint8_t *image, uint32_t *diff,
+                            uint32_t summary[2]);
+int cw_compare_witnesses_device(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const void *d_image, void *d_diff,
+                                void *d_summary);
+int cw_compare_witnesses_device_n8(cw_batch *b, uint32_t entry0, uint32_t n, uint32_t first, uint32_t count, const void *d_image,
+                                   void *d_diff, void *d_summary);
+int cw_compare_wtns(cw_batch *b, uint32_t instance, const char *path, uint32_t *diff);
+int cw_compare_wtns_many(cw_batch *b, uint32_t first, uint32_t count, const char *pattern, uint32_t *diff, uint32_t summary[2]);
 /* host-only: build and hazard-check the LDS staging plan of the R1CS check kernel for `chunks` row chunks
    and `entries` 2-KiB LDS entries per wave (0 = the defaults cw_batch_create would pick for `batch`).
    out[8] = {chunks, loads, terms, filler loads, distinct wires, entries, prefetch depth, 0}. */
